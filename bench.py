@@ -22,10 +22,20 @@ finalize); the one standalone k_finalize per 16-round chunk fal
 (profiles/pmc_cfg4.json, FETCH_SIZE x 2 + WRITE_SIZE, tools/traffic_json.py); it is reported only
 when that summary was taken on this build (same library sha256, or the same sha256 of the kernel
 sources: a rebuild of unchanged sources is not byte-identical), else null.
-cpu_baseline times the CPU oracle (this repo's spec restatement, oracle/) on rank 0 on a bounded
-sample of the same workload.
 
-Extra legs (every N, each guarded: a failing leg is reported as an error string and never costs
+A plain run (`--gpus N --steps K --warmup W`) does only what the headline needs: it creates the
+handle, warms up, times the K rounds, writes its outputs when `--dump-outputs DIR` is given and
+prints the line.  `--dump-outputs DIR` writes what the timed rounds left with their caller as
+float32 / float64 .npy files (dump_outputs() below: the node values after the last timed round,
+a fixed seeded sample of them above 64 MB, and the last round's info); the workload is seeded, so
+two builds run with the same arguments can be compared output for output.
+
+Everything else runs only with `--full`, after the headline: `parity` (the headline workload for
+100 FIXED rounds on a fresh handle against the oracle's golden hash), the extra legs below and
+cpu_baseline, which times the CPU oracle (this repo's spec restatement, oracle/) on rank 0 on a
+bounded sample of the same workload.
+
+Extra legs (--full; every N, each guarded: a failing leg is reported as an error string and never costs
 the headline line; each result, and at N > 1 each cfg5 sub-leg, enters the line as soon as it
 exists, and a watchdog prints the line — naming the stage that hung — if a leg hangs).  Exit code:
 0 when every leg ran and matched its golden hash, 4 when one failed or mismatched (`legs_failed`
@@ -76,15 +86,24 @@ CFG3_FLOP_PER_NODE_ROUND = 128   # 2*64
 # SQ_ACTIVE_INST_VALU counts quad-cycles, so x 4 gives the SIMD-cycles the VALU pipe was busy
 VALU_PEAK_SIMD_CYCLES_PER_S = 1024 * 2.4e9
 GOLDEN = os.path.join(ROOT, "tests", "golden", "fullsize.json")
+ALL_LEGS = "f32,cfg3,cfg5,narrow"
+DUMP_MAX_BYTES = 64 * 1000 * 1000   # --dump-outputs: all files together stay below this
+DUMP_SAMPLE_SEED = 20240  # fixed: two builds dump the same node sample
 
 
-def parse():
+def parse(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--warmup", type=int, default=10)
     p.add_argument("--n-nodes", type=int, default=1 << 20)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, also run what a plain run leaves out: the 100-round golden "
+                        "check of the headline workload, the extra legs (--legs) and cpu_baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what they computed (rank 0: the node values and the "
+                        "last round's info) as DIR/<name>.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     p.add_argument("--dtype", default="f64", choices=["f64", "f32"],
                    help="value type; the headline is fp64, fp32 mode (DESIGN.md §9) is reported separately")
     p.add_argument("--cpu-seconds", type=float, default=20.0,
@@ -94,14 +113,20 @@ def parse():
     p.add_argument("--event-run", type=int, default=25,
                    help="bracket runs of k consecutive timed rounds with one HIP event pair each "
                         "(per-round device time with no event-induced idle inside a run)")
-    p.add_argument("--legs", default="f32,cfg3,cfg5,narrow",
-                   help="comma-separated extra legs (f32, cfg3, cfg5, narrow); empty for none")
+    p.add_argument("--legs", default=None,
+                   help="with --full: comma-separated extra legs (f32, cfg3, cfg5, narrow; default: all "
+                        "four); empty for none")
     p.add_argument("--leg-timeout", type=float, default=180.0,
                    help="watchdog: print the line without the unfinished legs after this many seconds")
     p.add_argument("--allow-shared-device", action="store_true",
                    help="rehearsal only: run more ranks than GPUs (n_gpus then counts distinct devices "
                         "and the line is marked shared_device)")
-    return p.parse_args()
+    a = p.parse_args(argv)
+    if a.legs and not a.full:
+        p.error("--legs needs --full (a plain run times the headline only)")
+    if a.legs is None:
+        a.legs = ALL_LEGS if a.full else ""
+    return a
 
 
 def host_facts() -> dict:
@@ -235,6 +260,41 @@ def load_pmc(kernel: str, n_nodes: int, dtype: str = "f64"):
     if d.get("lib_sha256") == lib_sha256() or d.get("src_sha256") == src_sha256():
         return d.get("hbm_bytes_per_launch")
     return None
+
+
+def dump_sample(n: int, itemsize: int, budget: int):
+    """The nodes whose values --dump-outputs writes: None (every node) when they fit in `budget`
+    bytes, else a fixed, seeded, sorted sample without replacement, the same for every run and
+    build (each sampled value is stored with its node index as a float64)."""
+    import numpy as np
+    if n * itemsize <= budget:
+        return None
+    keep = budget // (itemsize + 8)
+    return np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=keep, replace=False))
+
+
+def dump_outputs(path: str, x, info) -> dict:
+    """Write what the timed rounds left with their caller, as float32 / float64 .npy files of at
+    most DUMP_MAX_BYTES together:
+      values.npy        the node values x after the last timed round (instance 0; float64, or
+                        float32 in fp32 mode), or the sample of them named by
+      values_index.npy  the sampled node indices (only when x is larger than the limit);
+      round_info.npy    what the last round(k) call returned: round, done, spread, lo, hi,
+                        instances_done."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    files = {}
+    idx = dump_sample(x.size, x.dtype.itemsize, DUMP_MAX_BYTES - 4096)
+    if idx is not None:
+        files["values_index"] = idx.astype(np.float64)
+        x = x[idx]
+    files["values"] = np.ascontiguousarray(x)
+    files["round_info"] = np.array([info.round, info.done, info.spread, info.lo, info.hi,
+                                    info.instances_done], dtype=np.float64)
+    for name, arr in files.items():
+        assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+        np.save(os.path.join(path, name + ".npy"), arr)
+    return {"dir": path, "files": {k: list(v.shape) for k, v in files.items()}}
 
 
 class Ctx:
@@ -622,7 +682,7 @@ def main():
     sim.set_kernel_timing(not a.no_event_timing, every=a.event_run, runs=True)
     ctx.barrier(sim)
     t0 = time.perf_counter()
-    sim.round(a.steps)
+    last = sim.round(a.steps)
     ctx.barrier(sim)
     dt = time.perf_counter() - t0
     dt_local = dt
@@ -631,9 +691,12 @@ def main():
     rounds = int(sim.rounds()[0])
     assert rounds == a.warmup + a.steps, (rounds, a.warmup, a.steps)
     dt = ctx.max(dt)
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        dumped = dump_outputs(a.dump_outputs, sim.values(0), last)
     sim.close()
     headline_check = None
-    if rank == 0 and a.dtype == "f64" and n == 1 << 20:
+    if a.full and rank == 0 and a.dtype == "f64" and n == 1 << 20:
         # the bench workload's kernels, run for exactly 100 rounds on a fresh handle (untimed),
         # against the oracle's result (tests/golden/fullsize.json)
         from acsim.digest import sha256_values
@@ -672,10 +735,14 @@ def main():
         "hbm_roofline_pct_wall": 100.0 * unit_b * value / n_gpus / 1e9 / HBM_PEAK_GBS,
         "cpu_baseline": None,
         "parity": {"golden_match": headline_check,
-                   "what": "cfg4 run for 100 FIXED rounds on a fresh handle after the timed region: "
-                           "sha256(x) equals the oracle's (tests/golden/fullsize.json "
-                           "cfg4.fixed100_x_sha256); null for other shapes (--dtype f32, --n-nodes)"},
+                   "what": "with --full: cfg4 run for 100 FIXED rounds on a fresh handle after the timed "
+                           "region: sha256(x) equals the oracle's (tests/golden/fullsize.json "
+                           "cfg4.fixed100_x_sha256); null in a plain run and for other shapes "
+                           "(--dtype f32, --n-nodes)"},
+        "full": a.full,
     }
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if world > ndev:
         # rehearsal: several ranks time replicas on one card; no aggregate is a throughput result
         out["shared_device"] = True
@@ -733,7 +800,7 @@ def main():
         ctx.stage = "cpu_baseline"
     if rank == 0:
         out["legs_failed"] = failed
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(n, a.cpu_seconds, a.dtype)
         except Exception as e:  # noqa: BLE001

@@ -81,6 +81,46 @@ def test_other_ranks_return_nothing(monkeypatch):
     assert out == {} and len(seen) == 2   # every rank runs both sub-legs (RCCL needs all ranks)
 
 
+def test_plain_run_has_no_legs_and_full_has_all():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.legs, a.dump_outputs) == (7, 2, False, "", None)
+    assert bench.parse(["--legs="]).legs == ""     # what the profiling scripts pass
+    assert bench.parse(["--full"]).legs == bench.ALL_LEGS
+    assert set(bench.ALL_LEGS.split(",")) == set(bench.LEGS)
+    assert bench.parse(["--full", "--legs="]).legs == ""
+    assert bench.parse(["--full", "--legs", "cfg3"]).legs == "cfg3"
+    with pytest.raises(SystemExit):
+        bench.parse(["--legs", "cfg3"])
+
+
+def test_dump_sample_is_fixed_and_fits():
+    import numpy as np
+    assert bench.dump_sample(1000, 8, 8000) is None
+    idx = bench.dump_sample(1001, 8, 8000)
+    assert idx.size == 500 and idx.size * (8 + 8) <= 8000
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < 1001
+    assert np.array_equal(idx, bench.dump_sample(1001, 8, 8000))
+
+
+def test_dump_outputs_files(tmp_path, monkeypatch):
+    import numpy as np
+    from acsim.sim import RoundInfo
+    info = RoundInfo(25, False, 0.125, -1.5, 2.5, 0)
+    x = np.arange(5000, dtype=np.float32) / 3
+    rec = bench.dump_outputs(str(tmp_path / "a"), x, info)
+    assert rec["files"] == {"values": [5000], "round_info": [6]}
+    got = np.load(tmp_path / "a" / "values.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x)
+    assert np.load(tmp_path / "a" / "round_info.npy").tolist() == [25.0, 0.0, 0.125, -1.5, 2.5, 0.0]
+    # above the size limit: a sample and its node indices, within the limit together
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096 + 12000)
+    bench.dump_outputs(str(tmp_path / "b"), x, info)
+    idx = np.load(tmp_path / "b" / "values_index.npy")
+    assert idx.dtype == np.float64 and idx.size == 1000
+    assert np.array_equal(np.load(tmp_path / "b" / "values.npy"), x[idx.astype(np.int64)])
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= 4096 + 12000
+
+
 def test_enter_records_the_stage(monkeypatch):
     monkeypatch.delenv("ACSIM_BENCH_HANG", raising=False)
     ctx = FakeCtx()

@@ -8,8 +8,8 @@ mkdir -p "$out"
 export TMPDIR=/tmp
 cd /tmp
 B="$GRAFT_REPO_ROOT/bench.py"
-timeout -k 10 300 python3 "$B" > "$out/bench_f64.json" 2> "$out/bench_f64.err" || exit $?
-timeout -k 10 300 python3 "$B" --dtype f32 > "$out/bench_f32.json" 2> "$out/bench_f32.err" || exit $?
+timeout -k 10 300 python3 "$B" --full > "$out/bench_f64.json" 2> "$out/bench_f64.err" || exit $?
+timeout -k 10 300 python3 "$B" --full --dtype f32 > "$out/bench_f32.json" 2> "$out/bench_f32.err" || exit $?
 for dt in f64 f32; do
   timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats_$dt" -o run -- \
       python3 "$B" --no-cpu-baseline --legs= --dtype $dt > "$out/stats_$dt.log" 2>&1 || exit $?
