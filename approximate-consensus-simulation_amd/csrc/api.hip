@@ -246,6 +246,38 @@ static bool env_off(const char* name) {
     return v && v[0] == '0';
 }
 
+// The binned exchange's knobs (engine.hpp BinnedOptions), read once per acs_create: tests change them
+// between handles of one process.
+BinnedOptions acs::binned_options_from_env(bool f32) {
+    BinnedOptions o;
+    const char* v;
+    if ((v = getenv("ACSIM_BINNED"))) o.enabled = v[0] != '0';
+    // 128 KiB of LDS per phase-A source block: 16 Ki fp64 or 32 Ki fp32 senders (anything else: the default)
+    if ((v = getenv("ACSIM_BIN_SA"))) {
+        const uint32_t sa = (uint32_t)strtoul(v, nullptr, 10);
+        if (sa >= 64 && sa <= (f32 ? 32768u : 16384u) && !(sa & (sa - 1))) o.sa = sa;
+    }
+    if ((v = getenv("ACSIM_BIN_SB"))) o.sb = (uint32_t)strtoul(v, nullptr, 10);
+    if ((v = getenv("ACSIM_BIN_SPLIT"))) {   // (anything but 1..4: one pass)
+        o.split = (uint32_t)strtoul(v, nullptr, 10);
+        if (o.split < 1 || o.split > 4) o.split = 1;
+    }
+    if ((v = getenv("ACSIM_BIN_PACK"))) o.pack = (uint32_t)strtoul(v, nullptr, 10);
+    if ((v = getenv("ACSIM_BIN_POL"))) {
+        o.pol_set = true;
+        o.pol = (uint32_t)strtoul(v, nullptr, 0);
+    }
+    if ((v = getenv("ACSIM_BIN_MIMG")) && strtod(v, nullptr) > 0) o.mimg = strtod(v, nullptr);
+    if ((v = getenv("ACSIM_BIN_AWG"))) o.awg = strtoull(v, nullptr, 10);
+    o.nofix = getenv("ACSIM_BIN_NOFIX") != nullptr;
+    if ((v = getenv("ACSIM_BIN_NARROW"))) o.narrow = v[0] == '1';
+    if ((v = getenv("ACSIM_BIN_TS"))) {
+        o.ts = true;
+        o.ts_file = v;
+    }
+    return o;
+}
+
 static uint32_t drop_threshold(double p) {
     const double t = floor(p * 4294967296.0);   // §A.5, in fp64
     if (t <= 0.0) return 0u;
@@ -580,12 +612,15 @@ static int enqueue_round(acs_sim* s, uint32_t r) {
     // eacc[(r + 1) & 1], so every workgroup of round r + 1's phase A can stop on convergence
     // (without it only workgroup 0 folds the partials and the others stream one last round).
     // Invariant: EVERY kernel that writes a.partial in such a round must also publish into ab.eacc
-    // (block_minmax_store(..., a.eacc)): k_bin_gather in all its forms (NP = 1 / 2, VAR, FIX,
-    // FAULTY) and k_bin_gather_of.  A writer that skipped it would not crash: phase A's other
+    // (block_minmax_store(..., a.eacc)): k_bin_gather in all its forms (NP = 1 .. 4, VAR, FIX,
+    // FAULTY, the narrow NAR kernels and the 128- / 512-receiver blocks: every row of kGatherTable,
+    // binned_select.hpp).  A writer that skipped it would not crash: phase A's other
     // workgroups would stop on a stale verdict while workgroup 0 streams.  Hub rows (generic
     // kernel partials) and partitioned rounds are therefore excluded here;
     // tests/test_gpu_binned.py::test_eps_publication_in_every_gather_variant covers each form.
-    // (narrow plans publish in every round: the next phase A chooses its stage width from the pair)
+    // Narrow plans publish in every round, whatever the termination: the next phase A chooses its
+    // stage width and base from the pair, so there publication is needed for correct values, not
+    // only for the early stop.
     unsigned long long* pub = s->eacc && s->binned && s->defer_fin && !s->n_hub && !s->partitioned &&
                                       (s->c.termination == ACS_TERM_EPS || s->bin.narrow)
                                   ? s->eacc + kEaccWords * ((r + 1) & 1u)
@@ -1091,24 +1126,20 @@ static int create_impl(const acs_config* cfg, int device, int nranks, int rank, 
     // binned exchange (round_binned.hip): one instance, synchronous rounds, and a graph shape with
     // one or two exchange levels (faults and loss are resolved in phase B from tagged values and
     // slot-order draws); ACSIM_BINNED=0 forces the per-lane kernel and ACSIM_BIN_SA sets the
-    // source block size (tests use small blocks on small graphs)
-    // (128 KiB of LDS per phase-A source block: 16 Ki fp64 or 32 Ki fp32 senders).  Default 16 Ki for
+    // source block size (tests use small blocks on small graphs).  Default 16 Ki for
     // fp32 too: 14-bit packed phase-A indices, and measured faster (cfg4_f32 82.2 -> 80.9 us per round,
     // cfg5_f32 4.69 -> 4.51 ms; profiles/r04_f32_sa_ab.jsonl); ACSIM_BIN_SA up to 32 Ki
-    const uint32_t sa_max = s->f32 ? 32768u : 16384u;
-    uint32_t bin_sa = 16384u;
-    if (const char* v = getenv("ACSIM_BIN_SA")) bin_sa = (uint32_t)strtoul(v, nullptr, 10);
-    if (bin_sa < 64 || bin_sa > sa_max || (bin_sa & (bin_sa - 1))) bin_sa = 16384u;
+    const BinnedOptions bopt = binned_options_from_env(s->f32);
+    const uint32_t bin_sa = bopt.sa;
     // (the order-free phase B of rounds 1-5, ACSIM_BIN_OF=1, measured slower than the invpos phase
     // B and was removed in round 6: DESIGN.md §5.1, §5.13)
     std::string kname_lane;   // (set with the binned decision below)
     // phase-B receiver block (BinnedPlan::SB): the default, or ACSIM_BIN_SB where the clean (d, t)
     // pair has that instantiation; block partials follow it (one per receiver block)
-    const uint32_t bin_sb = binned_block_size(s->d, cfg->trim, cfg->rule,
+    const uint32_t bin_sb = binned_block_size(bopt, s->d, cfg->trim, cfg->rule,
                                               s->clean && !s->csr_var && s->path == PATH_REGULAR);
     {
-        const char* env = getenv("ACSIM_BINNED");
-        const bool allow = !(env && env[0] == '0');
+        const bool allow = bopt.enabled;
         const uint32_t lv =
             s->path == PATH_REGULAR && s->d ? binned_levels(s->N, rows_local, s->d, bin_sa, bin_sb, nullptr) : 0;
         // fp32 tags carry a 20-bit sender field: above 2^20 nodes a crash schedule stores crash ranks
@@ -1236,6 +1267,13 @@ static int create_impl(const acs_config* cfg, int device, int nranks, int rank, 
             CREATE_TRY(hipMemcpy(s->clist, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         }
     }
+    // what a binned plan of nr local rows is built for.  Narrow stage (ACSIM_BIN_NARROW=1, opt-in;
+    // DESIGN.md §5.15): whole unpartitioned rounds with the deferred finalize, whose phase B publishes
+    // each round's (min, max) for the next phase A
+    auto bin_desc = [&](uint64_t nr) {
+        return BinnedDesc{s->N, nr, s->d, s->dp, tagged, s->f32, s->csr_var, s->clean, s->status,
+                          !partitioned && s->defer_fin && s->eacc != nullptr};
+    };
     if (cfg->topology == ACS_TOPO_RANDOM_REGULAR) {
         const uint64_t words = ((rows_local + 63) / 64) * 64ull * s->dp;
         CREATE_TRY(hipMalloc(&s->ell, words * sizeof(uint32_t)));
@@ -1246,14 +1284,9 @@ static int create_impl(const acs_config* cfg, int device, int nranks, int rank, 
         // per receiver block): then every partition keeps its ELL and runs the per-lane kernel,
         // which serves the same configs (binned_supported implies a compiled register variant).
         bool bin_refused = false;
-        // narrow stage (ACSIM_BIN_NARROW=1, opt-in): whole unpartitioned rounds with
-        // the deferred finalize, whose phase B publishes each round's (min, max) for the next phase A
-        const char* nar_env = getenv("ACSIM_BIN_NARROW");
-        const bool want_narrow = nar_env && nar_env[0] == '1' && !partitioned && s->defer_fin && s->eacc;
         auto try_plan = [&](BinnedPlan& plan, const uint32_t* ell, uint64_t nr) -> hipError_t {
             if (!s->binned || bin_refused || !nr) return hipSuccess;
-            hipError_t e = binned_build(plan, ell, s->N, nr, s->d, s->dp, bin_sa, bin_sb, tagged, s->f32, s->stream,
-                                        false, s->status, s->clean, want_narrow);
+            hipError_t e = binned_build(plan, ell, bin_desc(nr), bopt, bin_sb, s->stream);
             if (e == hipErrorNotSupported) {
                 bin_refused = true;
                 return hipSuccess;
@@ -1315,8 +1348,7 @@ static int create_impl(const acs_config* cfg, int device, int nranks, int rank, 
             CREATE_TRY(launch_csr_to_ell(s->rowptr, s->colidx, s->N, s->d, s->ell, s->deg, s->sw, s->stream));
             if (s->ell_sorted) CREATE_TRY(launch_sort_ell_rows(s->ell, s->N, s->d, s->stream));
             if (s->binned) {
-                const hipError_t be = binned_build(s->bin, s->ell, s->N, s->N, s->d, s->dp, bin_sa, kBinSB, tagged,
-                                                   s->f32, s->stream, true, s->status);
+                const hipError_t be = binned_build(s->bin, s->ell, bin_desc(s->N), bopt, kBinSB, s->stream);
                 if (be == hipErrorNotSupported) {   // the plan does not fit: the per-lane kernel serves the rows
                     binned_free(s->bin);
                     s->binned = false;

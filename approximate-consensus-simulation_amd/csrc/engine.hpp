@@ -13,11 +13,13 @@
 //   trace     : f64 [B][max_rounds+1] optional spread trace
 #pragma once
 
+#include <string>
 #include <utility>
 #include <vector>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "binned_select.hpp"
 #include "spec.hpp"
 
 namespace acs {
@@ -181,13 +183,31 @@ constexpr uint32_t kRegularBlock = 256;
 // values through invpos and applies the rule in registers.
 // Receivers per phase-B workgroup (one lane each) is a property of the plan (BinnedPlan::SB), not a
 // build constant: the phase-B grid, invpos layout, tiles and the block-partial slots all follow
-// it (one partial per receiver block, so a handle sizes its partials by the plan's SB).  kBinSB is
-// the default; clean fp64 / fp32 plans of d = 16 / 32 also take 128 (and d = 16 512), by
-// ACSIM_BIN_SB or the per-degree default (binned_block_size).
-constexpr uint32_t kBinSB = 256;
-bool binned_sb_supported(uint32_t d, uint32_t t, uint32_t rule, uint32_t sb, bool clean_fast);
-// the phase-B receiver block a plan of degree d would use (ACSIM_BIN_SB, else the default for d)
-uint32_t binned_block_size(uint32_t d, uint32_t t, uint32_t rule, bool clean_fast);
+// it (one partial per receiver block, so a handle sizes its partials by the plan's SB).  kBinSB
+// (binned_select.hpp) is the default of every plan.  ACSIM_BIN_SB is the only way to choose another:
+// 128 for clean t = 5 plans of d = 16 / 32 under a sort-based rule other than W-MSR, 512 for those
+// of d = 16 (binned_sb_supported, derived from the compiled phase-B set).
+//
+// The binned knobs of the environment, read once per acs_create (binned_options_from_env) and
+// handed to whoever needs them; nothing else on the binned path reads the environment.
+struct BinnedOptions {
+    bool enabled = true;       // ACSIM_BINNED: 0 forces the per-lane kernel
+    uint32_t sa = 16384;       // ACSIM_BIN_SA: source block, a power of two in [64, 16 Ki (fp32: 32 Ki)]
+    uint32_t sb = kBinSB;      // ACSIM_BIN_SB: receiver block asked for (binned_block_size decides)
+    uint32_t split = 0;        // ACSIM_BIN_SPLIT: phase-B passes 1..4 (0: unset, 2 for fp64 d = 32, else 1)
+    uint32_t pack = 1;         // ACSIM_BIN_PACK: bit 0: 14-bit packed phase-A index stream
+    bool pol_set = false;      // ACSIM_BIN_POL: cache-policy switches in place of the plan's default
+    uint32_t pol = 0;
+    double mimg = 16384.0;     // ACSIM_BIN_MIMG: target deliveries per phase-M image
+    uint64_t awg = 0;          // ACSIM_BIN_AWG: phase-A workgroups per launch (0: the plan's choice)
+    bool nofix = false;        // ACSIM_BIN_NOFIX: tagged senders even where a fix-up list would serve
+    bool narrow = false;       // ACSIM_BIN_NARROW=1: narrow stage where the plan qualifies
+    bool ts = false;           // ACSIM_BIN_TS=<file>: workgroup timestamps, dumped when the plan is freed
+    std::string ts_file;
+};
+BinnedOptions binned_options_from_env(bool f32);
+// the phase-B receiver block a plan would use: opt.sb where (d, t, rule) has it, else kBinSB
+uint32_t binned_block_size(const BinnedOptions& opt, uint32_t d, uint32_t t, uint32_t rule, bool clean_fast);
 struct BinnedPlan {
     uint32_t D = 0, SA = 0, P = 0, Q = 0, levels = 0, PK = 0, ngroups = 0, nrun = 0, mcap = 0;
     uint32_t SB = kBinSB;               // receivers per phase-B workgroup (receiver block)
@@ -202,7 +222,7 @@ struct BinnedPlan {
     uint2* tiles = nullptr;             // [Q][nrun+1] (stage start | pad count, element offset in block b's runs)
     bool var = false;                   // CSR rows below the compiled degree (kEllNone columns)
     uint32_t split = 1;                 // phase-B passes over the image (ACSIM_BIN_SPLIT; 1 = whole image)
-    uint32_t pol = 0;                   // cache-policy switches (round_binned.hip kPol*)
+    uint32_t pol = 0;                   // cache-policy switches (binned_dev.hpp kPol*)
     uint2* mt = nullptr;                // [ngroups][PK+1] phase-M run tables (two levels)
     uint64_t* aoff = nullptr;           // [P+1] stage1 start of source block a
     uint64_t* moff = nullptr;           // [ngroups+1] stage2 start of phase-M group g
@@ -210,6 +230,7 @@ struct BinnedPlan {
     double* stage2 = nullptr;           // [Ep2] (two levels)
     double* xtag = nullptr;             // [N+2] tagged sender values (fault schedules only)
     uint64_t* ts = nullptr;             // ACSIM_BIN_TS=<file>: [3 * (ts_a + ts_b + ts_m)] workgroup timestamps of the last round
+    std::string ts_file;                // the file binned_free dumps them into
     uint32_t ts_a = 0, ts_b = 0, ts_m = 0;   // phase-A / phase-B / phase-M workgroups recorded
     // fault fix-up: fix[k] = (last-stage position, local row, slot, sender) of every
     // delivery from a sender that is not honest; nullptr: tagged senders (k_bin_tag) instead
@@ -224,13 +245,22 @@ struct BinnedPlan {
 bool binned_supported(uint32_t d, uint32_t t, uint32_t rule);
 // 1 or 2 exchange levels for NR local receivers of an N-node graph (0: not supported); sb = receiver block.
 uint32_t binned_levels(uint64_t N, uint64_t NR, uint32_t d, uint32_t sa, uint32_t sb, uint32_t* sr_out);
+// What a plan is built for: NR local rows of an N-node graph of degree d (ELL row width dp).
+struct BinnedDesc {
+    uint64_t N, NR;
+    uint32_t d, dp;
+    bool tagged;              // the config has a fault schedule
+    bool f32;
+    bool var;                 // CSR rows below the compiled degree (kEllNone columns)
+    bool clean;               // no slot-dependent decision
+    const uint32_t* status;   // [N] fault status (the fix-up list), or nullptr
+    bool narrow;              // whole unpartitioned rounds with a published (min, max): a narrow plan may serve
+};
 // Builds the plan from the ELL of the NR local rows (sorted or spec order; slot-dependent configs
-// need spec order); sa = source block size; sb = receiver block (binned_block_size; must satisfy
-// binned_sb_supported); tagged: the config has a fault schedule.
-// narrow: build a narrow plan where the plan qualifies (p.narrow says whether it did).
-hipError_t binned_build(BinnedPlan& p, const uint32_t* ell, uint64_t N, uint64_t NR, uint32_t d, uint32_t dp,
-                        uint32_t sa, uint32_t sb, bool tagged, bool f32, hipStream_t s, bool var = false,
-                        const uint32_t* status = nullptr, bool clean = false, bool narrow = false);
+// need spec order); sb = receiver block (binned_block_size).  A narrow plan is built where
+// opt.narrow and desc.narrow ask for one and the plan qualifies (p.narrow says whether it did).
+hipError_t binned_build(BinnedPlan& p, const uint32_t* ell, const BinnedDesc& desc, const BinnedOptions& opt,
+                        uint32_t sb, hipStream_t s);
 void binned_free(BinnedPlan& p);
 // clean: no slot-dependent decision (selects the plain phase-B instantiation)
 // fin: the previous round's finalize, deferred into this round's phase A (nullptr: none pending)
