@@ -6,6 +6,7 @@
   python -m acsim sweep --preset cfg3 --set n_instances=1000 --grid loss_p=0.1,0.2 --out runs/
   python -m acsim run --preset cfg4 --graph my_graph.npz --set trim=2 ...   (user CSR graph,
       acsim or scipy.sparse .npz layout; topology and n_nodes come from the file)
+  python -m acsim run --graph weighted.npz --set rule=weighted ...   (the file's weights too)
 """
 from __future__ import annotations
 
@@ -14,6 +15,8 @@ import ctypes as C
 import dataclasses
 import json
 import sys
+
+import numpy as np
 
 from . import _abi
 from .config import PRESETS, Config, preset
@@ -48,12 +51,19 @@ def _grid(specs):
     return grid
 
 
-def validate(cfg: Config, csr=None) -> int:
+def validate(cfg: Config, csr=None, weights=None) -> int:
     """Host-side §A.8 validation through the library (no GPU needed: acs_create validates first)."""
     lib = _abi.load_library()
     c = cfg.to_c()
     h = C.c_void_p()
-    if csr is not None:
+    if csr is not None and weights is not None:
+        rp, ci = csr
+        ws, we = (np.ascontiguousarray(w, dtype=np.float64) for w in weights)
+        dp = C.POINTER(C.c_double)
+        rc = lib.acs_create_csr_weighted(C.byref(c), rp.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                         ci.ctypes.data_as(C.POINTER(C.c_uint32)), ws.ctypes.data_as(dp),
+                                         we.ctypes.data_as(dp), 0, C.byref(h))
+    elif csr is not None:
         rp, ci = csr
         rc = lib.acs_create_csr(C.byref(c), rp.ctypes.data_as(C.POINTER(C.c_uint64)),
                                 ci.ctypes.data_as(C.POINTER(C.c_uint32)), 0, C.byref(h))
@@ -89,27 +99,32 @@ def main(argv=None) -> int:
             print(k, json.dumps(dataclasses.asdict(v)))
         return 0
     cfg = _apply(preset(a.preset), a.set)
-    csr = None
+    csr = weights = None
     if a.graph:
+        from .config import _enum
         from .graphs import load_csr
-        csr = load_csr(a.graph)
+        if _enum("rule", cfg.rule) == _abi.RULE_WEIGHTED:   # the file's weights go with the rule
+            g = load_csr(a.graph, weights=True)
+            csr, weights = g[:2], g[2:]
+        else:
+            csr = load_csr(a.graph)
         cfg = cfg.replace(topology="csr", n_nodes=int(csr[0].size - 1))
     if a.cmd == "validate":
-        rc = validate(cfg, csr)
+        rc = validate(cfg, csr, weights)
         if rc == 0:
             print("ok")
         return rc
     if a.cmd == "run":
         from .io import save_result
         from .sim import simulate
-        res = simulate(cfg, device=a.device, return_values=bool(a.out), csr=csr)
+        res = simulate(cfg, device=a.device, return_values=bool(a.out), csr=csr, weights=weights)
         from .sweep import summarize
         print(json.dumps(summarize(cfg, res)))
         if a.out:
             save_result(a.out, res, cfg)
         return 0
     from .sweep import sweep
-    rows = sweep(cfg, _grid(a.grid), out_dir=a.out, device=a.device, csr=csr)
+    rows = sweep(cfg, _grid(a.grid), out_dir=a.out, device=a.device, csr=csr, weights=weights)
     for r in rows:
         print(json.dumps(r))
     return 0

@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 # status codes
 OK, EINVAL, ENOMEM, EDEVICE, ECOMM, EUNSUPPORTED = 0, -1, -2, -3, -4, -5
@@ -20,7 +20,7 @@ BACKEND_CPU, BACKEND_HIP = 0, 1
 
 # topology / rule / faults / byz / termination / dtype
 TOPO_COMPLETE, TOPO_RANDOM_REGULAR, TOPO_CSR = 0, 1, 2
-RULE_AVERAGE, RULE_TRIMMED_MEAN, RULE_MIDPOINT, RULE_DLPSW_SELECT, RULE_WMSR = 0, 1, 2, 3, 4
+RULE_AVERAGE, RULE_TRIMMED_MEAN, RULE_MIDPOINT, RULE_DLPSW_SELECT, RULE_WMSR, RULE_WEIGHTED = 0, 1, 2, 3, 4, 5
 FAULT_NONE, FAULT_CRASH, FAULT_BYZANTINE = 0, 1, 2
 BYZ_SPLIT, BYZ_RANDOM, BYZ_CONSTANT = 0, 1, 2
 TERM_EPS, TERM_FIXED = 0, 1
@@ -111,6 +111,8 @@ def _declare(lib: C.CDLL) -> None:
     sigs = {
         "acs_create": (i32, [P(AcsConfig), i32, P(C.c_int), i32, P(vp)]),
         "acs_create_csr": (i32, [P(AcsConfig), P(u64), P(u32), i32, P(vp)]),
+        "acs_create_csr_weighted": (i32, [P(AcsConfig), P(u64), P(u32), P(C.c_double), P(C.c_double), i32, P(vp)]),
+        "acs_get_weights": (i32, [vp, P(C.c_double), u64, P(C.c_double), u64]),
         "acs_comm_id_size": (i32, []),
         "acs_get_comm_id": (i32, [vp, u64]),
         "acs_create_partitioned": (i32, [P(AcsConfig), i32, i32, i32, vp, u64, P(vp)]),

@@ -1,5 +1,6 @@
 """Synthetic user graphs in CSR form for the ACS_TOPO_CSR topology:
-``(rowptr uint64[N+1], colidx uint32[nnz])`` as ``acsim.Simulator(cfg, csr=...)`` takes them.
+``(rowptr uint64[N+1], colidx uint32[nnz])`` as ``acsim.Simulator(cfg, csr=...)`` takes them,
+and the edge weights of rule "weighted" (``weights=(w_self, w_edge)``).
 Used by the CSR benchmarks and tests; any CSR the caller builds works the same way."""
 from __future__ import annotations
 
@@ -33,22 +34,39 @@ def skewed_csr(n: int, dmin: int, dmax: int, seed: int, alpha: float = 2.0):
 # user graphs arrive as `.npz` files.  Two layouts are read:
 #   acsim's own      rowptr (uint64 [N+1]), colidx (uint32 [nnz])   (save_csr writes this)
 #   scipy.sparse     indptr, indices, shape, format = "csr"          (scipy.sparse.save_npz of a CSR
-#                    matrix whose row i lists receiver i's senders; `data` is ignored)
+#                    matrix whose row i lists receiver i's senders; `data` holds the edge
+#                    weights, read only when weights are asked for)
+# Weights (rule "weighted") are optional: acsim's layout adds w_self (float64 [N]) and
+# w_edge (float64 [nnz], by slot); in the scipy layout w_edge = data and w_self = 0 (a diagonal
+# entry is an ordinary self-loop message on its slot, with its own weight).
 # Receiver i's senders are colidx[rowptr[i] : rowptr[i+1]] in slot order (slot = rowptr[i] + t,
 # SURVEY §A.3).  Files are loaded with allow_pickle=False: a graph file executes nothing.
 
-def save_csr(path: str, rowptr, colidx) -> None:
-    """Write a CSR graph in acsim's `.npz` layout (validated first)."""
+def save_csr(path: str, rowptr, colidx, weights=None) -> None:
+    """Write a CSR graph in acsim's `.npz` layout (validated first); weights = (w_self, w_edge)
+    are stored beside it for rule "weighted"."""
     rp, ci = check_csr(rowptr, colidx)
-    np.savez(path, rowptr=rp, colidx=ci, format=np.array("acsim-csr-v1"))
+    extra = {}
+    if weights is not None:
+        ws, we = check_weights(rp, weights[0], weights[1])
+        extra = {"w_self": ws, "w_edge": we}
+    np.savez(path, rowptr=rp, colidx=ci, format=np.array("acsim-csr-v1"), **extra)
 
 
-def load_csr(path: str):
-    """Read a CSR graph file (acsim or scipy.sparse layout) -> (rowptr uint64[N+1], colidx uint32[nnz])."""
+def load_csr(path: str, weights: bool = False):
+    """Read a CSR graph file (acsim or scipy.sparse layout) -> (rowptr uint64[N+1], colidx uint32[nnz]).
+    weights=True also returns the file's weights, (rowptr, colidx, w_self, w_edge): the arrays
+    w_self / w_edge of acsim's layout, or w_edge = data and w_self = 0 for a scipy.sparse matrix;
+    a file without weights is a ValueError."""
+    ws = we = None
     with np.load(path, allow_pickle=False) as z:
         keys = set(z.files)
         if {"rowptr", "colidx"} <= keys:
             rp, ci = z["rowptr"], z["colidx"]
+            if weights:
+                if not {"w_self", "w_edge"} <= keys:
+                    raise ValueError(f"{path}: no weights (w_self / w_edge) in {sorted(keys)}")
+                ws, we = z["w_self"], z["w_edge"]
         elif {"indptr", "indices"} <= keys:
             if "format" in keys and str(z["format"].astype(str)) != "csr":
                 raise ValueError(f"{path}: scipy.sparse matrix in {z['format']!s} format; CSR expected")
@@ -57,9 +75,61 @@ def load_csr(path: str):
                 shape = tuple(int(v) for v in z["shape"])
                 if shape[0] != shape[1] or shape[0] != rp.size - 1:
                     raise ValueError(f"{path}: adjacency must be N x N with N = len(indptr) - 1, got {shape}")
+            if weights:
+                if "data" not in keys:
+                    raise ValueError(f"{path}: no weights (data) in {sorted(keys)}")
+                we = z["data"]
+                ws = np.zeros(rp.size - 1)
         else:
             raise ValueError(f"{path}: no CSR arrays (rowptr/colidx or indptr/indices) in {sorted(keys)}")
-    return check_csr(rp, ci)
+    rp, ci = check_csr(rp, ci)
+    if weights:
+        return (rp, ci) + check_weights(rp, ws, we)
+    return rp, ci
+
+
+def check_weights(rowptr, w_self, w_edge):
+    """Shapes and type of a weight pair for the graph `rowptr` -> (float64 [N], float64 [nnz]).  The
+    value rules (finite, in [0, 1], positive row sums) belong to acs_create_csr_weighted."""
+    rp = np.asarray(rowptr)
+    ws = np.asarray(w_self)
+    we = np.asarray(w_edge)
+    for w in (ws, we):
+        if not (np.issubdtype(w.dtype, np.floating) or np.issubdtype(w.dtype, np.integer)):
+            raise ValueError("weights must be real numbers")
+    if ws.shape != (rp.size - 1,) or we.shape != (int(rp[-1]),):
+        raise ValueError("weights must be (w_self[N], w_edge[nnz])")
+    return ws.astype(np.float64), we.astype(np.float64)
+
+
+def metropolis_weights(rowptr, colidx):
+    """Metropolis-Hastings weights of a symmetric graph: w_ij = 1 / (1 + max(deg_i, deg_j)) on the
+    slot of every edge and w_ii = 1 - sum_j w_ij, so W is doubly stochastic and x' = W x keeps the
+    mean.  deg = entries per row.  Returns (w_self, w_edge)."""
+    rp, ci = check_csr(rowptr, colidx)
+    deg = np.diff(rp.astype(np.int64))
+    rows = np.repeat(np.arange(deg.size), deg)
+    we = 1.0 / (1.0 + np.maximum(deg[rows], deg[ci.astype(np.int64)]).astype(np.float64))
+    ws = 1.0 - np.bincount(rows, weights=we, minlength=deg.size)
+    return ws, we
+
+
+def scale_weights(w_self, w_edge):
+    """Scale every weight by one power of two: 1 if the largest weight is already at most 1, else
+    1 / 2^e with the smallest e that brings it to at most 1 (the library admits weights in [0, 1]).  The simulation's result does not change: a power-of-two
+    factor is exact on every product and on both tree sums, and cancels in the divide (short of
+    underflow, i.e. for weights above about 1e-290 after scaling).  Returns (w_self, w_edge)."""
+    ws = np.asarray(w_self, dtype=np.float64)
+    we = np.asarray(w_edge, dtype=np.float64)
+    top = max(float(ws.max(initial=0.0)), float(we.max(initial=0.0)))
+    if not np.isfinite(top) or top <= 1.0:
+        return ws.copy(), we.copy()
+    e = int(np.ceil(np.log2(top)))
+    while np.ldexp(top, -e) > 1.0:
+        e += 1
+    while e > 0 and np.ldexp(top, -(e - 1)) <= 1.0:
+        e -= 1
+    return np.ldexp(ws, -e), np.ldexp(we, -e)
 
 
 def check_csr(rowptr, colidx):

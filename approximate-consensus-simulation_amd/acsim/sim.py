@@ -44,11 +44,14 @@ class Simulator:
 
     def __init__(self, cfg: Config | str, device: int = 0, backend: str = "hip",
                  partitions: int = 1, rank: int = 0, comm_id: Optional[bytes] = None,
-                 csr=None):
+                 csr=None, weights=None):
         """partitions > 1 node-partitions one RANDOM_REGULAR instance: with
         comm_id (RCCL unique id from acsim.distributed) this handle is `rank`'s partition on
         `device`; without it all partitions are simulated on `device` with private x copies
-        (validation mode, see include/acsim.h acs_create_partitioned)."""
+        (validation mode, see include/acsim.h acs_create_partitioned).
+
+        weights = (w_self[N], w_edge[nnz]) with csr and rule="weighted" (DESIGN.md §9): receiver
+        i's own entry weighs w_self[i], the message on slot s weighs w_edge[s]."""
         if isinstance(cfg, str):
             cfg = preset(cfg)
         if backend != "hip":
@@ -59,7 +62,23 @@ class Simulator:
         self._lib = _abi.load_library()
         self._c = cfg.to_c()
         h = C.c_void_p()
-        if csr is not None:   # user graph (topology="csr"): csr = (rowptr[N+1], colidx[nnz])
+        if weights is not None and csr is None:
+            raise ValueError("weights need a csr graph")
+        if csr is not None and weights is not None:   # rule="weighted" (acs_create_csr_weighted)
+            rp = np.ascontiguousarray(csr[0], dtype=np.uint64)
+            ci = np.ascontiguousarray(csr[1], dtype=np.uint32)
+            ws = np.ascontiguousarray(weights[0], dtype=np.float64)
+            we = np.ascontiguousarray(weights[1], dtype=np.float64)
+            if rp.size != int(cfg.n_nodes) + 1:
+                raise ValueError("rowptr must have n_nodes + 1 entries")
+            if ws.shape != (int(cfg.n_nodes),) or we.shape != ci.shape:
+                raise ValueError("weights must be (w_self[n_nodes], w_edge[len(colidx)])")
+            self._nnz = int(ci.size)
+            dp = C.POINTER(C.c_double)
+            rc = self._lib.acs_create_csr_weighted(
+                C.byref(self._c), rp.ctypes.data_as(C.POINTER(C.c_uint64)), ci.ctypes.data_as(C.POINTER(C.c_uint32)),
+                ws.ctypes.data_as(dp), we.ctypes.data_as(dp), int(device), C.byref(h))
+        elif csr is not None:   # user graph (topology="csr"): csr = (rowptr[N+1], colidx[nnz])
             rp = np.ascontiguousarray(csr[0], dtype=np.uint64)
             ci = np.ascontiguousarray(csr[1], dtype=np.uint32)
             if rp.size != int(cfg.n_nodes) + 1:
@@ -185,6 +204,15 @@ class Simulator:
             self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size))
         return out.reshape(self.B, self.N)
 
+    def weights(self):
+        """(w_self[N], w_edge[nnz]) as the device holds them (rule="weighted"; with dtype="f32" the
+        weights rounded to binary32, returned as float64)."""
+        ws = np.empty(self.N, dtype=np.float64)
+        we = np.empty(getattr(self, "_nnz", 0), dtype=np.float64)
+        dp = C.POINTER(C.c_double)
+        self._chk(self._lib.acs_get_weights(self._h, ws.ctypes.data_as(dp), ws.size, we.ctypes.data_as(dp), we.size))
+        return ws, we
+
     def neighbors(self) -> np.ndarray:
         d = int(self.cfg.degree)
         out = np.empty(self.N * d, dtype=np.uint32)
@@ -215,7 +243,7 @@ class Simulator:
 
 def simulate(cfg: Config | str, backend: str = "hip", device: int = 0,
              devices: Optional[Sequence[int]] = None, return_values: bool = True,
-             csr=None) -> Result:
+             csr=None, weights=None) -> Result:
     """Run one configuration to termination and return its results."""
     if devices is not None:
         devices = list(devices)
@@ -223,7 +251,7 @@ def simulate(cfg: Config | str, backend: str = "hip", device: int = 0,
             raise ValueError("simulate() drives one device per process; shard instances across "
                              "processes with acsim.distributed (one rank per GPU)")
         device = devices[0]
-    with Simulator(cfg, device=device, backend=backend, csr=csr) as sim:
+    with Simulator(cfg, device=device, backend=backend, csr=csr, weights=weights) as sim:
         res = sim.run()
         x = None
         if return_values:

@@ -146,6 +146,12 @@ struct acs_sim {
     uint32_t gen_base = 0;
     uint64_t n_hub = 0;
     uint32_t nblk_fast = 0;
+    // rule WEIGHTED: weights of the config dtype, shared by all instances
+    bool weighted = false;
+    uint64_t nnz = 0;              // rowptr[N] (CSR handles)
+    void* wself = nullptr;         // [N]
+    void* wedge = nullptr;         // [nnz] slot order (generic kernel, acs_get_weights)
+    void* well = nullptr;          // the ELL's order (csr_var; RoundArgs::well)
     double* dsorted = nullptr;     // dense path: sorted base multiset [N]
     uint32_t* dcounts = nullptr;   // dense path: |B|, #Byzantine, #crash-silent
     std::vector<Part> parts;       // virtual partitions 1..P-1 (partition 0 uses x / ell)
@@ -190,8 +196,9 @@ static int validate(const acs_config* c) {
     }
     if (slots >= (1ull << 34)) return fail(ACS_EINVAL, "slot count must be < 2^34");
     if (c->topology == ACS_TOPO_CSR) {
-        if (c->rule > ACS_RULE_WMSR) return fail(ACS_EINVAL, "unknown rule %u", c->rule);
+        if (c->rule > ACS_RULE_WEIGHTED) return fail(ACS_EINVAL, "unknown rule %u", c->rule);
         if (c->rule == ACS_RULE_AVERAGE && c->trim != 0) return fail(ACS_EINVAL, "AVERAGE requires trim == 0");
+        if (c->rule == ACS_RULE_WEIGHTED && c->trim != 0) return fail(ACS_EINVAL, "WEIGHTED requires trim == 0");
         if (c->rule == ACS_RULE_DLPSW_SELECT && c->trim < 1) return fail(ACS_EINVAL, "DLPSW needs t >= 1");
     } else
     switch (c->rule) {
@@ -206,6 +213,8 @@ static int validate(const acs_config* c) {
         case ACS_RULE_DLPSW_SELECT:
             if (c->trim < 1 || m <= 2ull * c->trim) return fail(ACS_EINVAL, "DLPSW needs t >= 1, m > 2t");
             break;
+        case ACS_RULE_WEIGHTED:
+            return fail(ACS_EINVAL, "WEIGHTED needs a CSR graph with weights: use acs_create_csr_weighted");
         default:
             return fail(ACS_EINVAL, "unknown rule %u", c->rule);
     }
@@ -317,6 +326,9 @@ static void release(acs_sim* s) {
     (void)hipFree(s->colidx);
     (void)hipFree(s->deg);
     (void)hipFree(s->sw);
+    (void)hipFree(s->wself);
+    (void)hipFree(s->wedge);
+    (void)hipFree(s->well);
     (void)hipFree(s->gen_ids);
     (void)hipFree(s->crank);
     (void)hipFree(s->clist);
@@ -490,6 +502,9 @@ static RoundArgs round_args(acs_sim* s, uint32_t r) {
     a.crank = s->crank;
     a.clist = s->clist;
     a.coff = s->clist && r < s->coff.size() ? s->coff[r] : 0u;
+    a.wself = s->wself;
+    a.wedge = s->wedge;
+    a.well = s->well;
     return a;
 }
 
@@ -632,6 +647,8 @@ static int enqueue_round(acs_sim* s, uint32_t r) {
             if (s->n_hub) ab.qhi = s->nblk_fast;   // the hub rows' partial slots are the generic kernel's
             HIP_TRY(launch_round_binned(s->bin, ab, s->clean, s->stream, s->fin_pending ? &s->fin_args : nullptr));
             s->fin_pending = false;
+        } else if (s->path == PATH_REGULAR && s->weighted) {
+            HIP_TRY(launch_round_weighted(a, s->B, s->nblk_fast, s->stream));
         } else if (s->path == PATH_REGULAR) {
             HIP_TRY(launch_round_regular(a, s->B, s->clean, s->stream));
         } else if (s->path == PATH_DENSE) {
@@ -963,9 +980,14 @@ static int advance(acs_sim* s, uint32_t k) {
 
 // CSR on the register / binned paths (§8(f) row 1): the smallest compiled degree D >= the
 // largest row with the config's (t, rule), 0 if none (the generic kernel then runs).
+// (rule WEIGHTED has its own per-lane kernel, k_round_weighted<D>, over the same padded rows)
+static bool csr_width_compiled(uint32_t d, uint32_t t, uint32_t rule) {
+    return rule == ACS_RULE_WEIGHTED ? t == 0 && weighted_fast_supported(d) : regular_fast_supported(d, t, rule);
+}
+
 static uint32_t csr_fast_degree(uint64_t maxdeg, uint32_t t, uint32_t rule) {
     for (uint32_t d : {4u, 8u, 16u, 32u})
-        if (d >= maxdeg && regular_fast_supported(d, t, rule)) return d;
+        if (d >= maxdeg && csr_width_compiled(d, t, rule)) return d;
     return 0;
 }
 
@@ -974,7 +996,7 @@ static uint32_t csr_fast_degree(uint64_t maxdeg, uint32_t t, uint32_t rule) {
 // The hub rows go to the generic kernel, the rest to the register / binned path padded to d.
 static uint32_t csr_hub_degree(const uint64_t* rowptr, uint64_t N, uint32_t t, uint32_t rule, uint64_t* nhub) {
     for (uint32_t d : {32u, 16u, 8u, 4u}) {
-        if (!regular_fast_supported(d, t, rule)) continue;
+        if (!csr_width_compiled(d, t, rule)) continue;
         uint64_t h = 0;
         for (uint64_t i = 0; i < N; ++i) h += rowptr[i + 1] - rowptr[i] > d;
         if (h * 4 <= N) {
@@ -999,7 +1021,8 @@ static hipError_t build_rows(acs_sim* s, uint32_t* ell, int p) {
 
 static int create_impl(const acs_config* cfg, int device, int nranks, int rank, const void* comm_id,
                        uint64_t id_len, acs_sim** out, const uint64_t* h_rowptr = nullptr,
-                       const uint32_t* h_colidx = nullptr) {
+                       const uint32_t* h_colidx = nullptr, const double* h_wself = nullptr,
+                       const double* h_wedge = nullptr) {
     if (!out) return fail(ACS_EINVAL, "null out");
     *out = nullptr;
     int rc = validate(cfg);
@@ -1025,6 +1048,37 @@ static int create_impl(const acs_config* cfg, int device, int nranks, int rank, 
             return fail(ACS_EINVAL, "BYZ RANDOM needs slot count <= 2^33");
         for (uint64_t k = 0; k < csr_nnz; ++k)
             if (h_colidx[k] >= N) return fail(ACS_EINVAL, "colidx[%llu] out of range", (unsigned long long)k);
+    }
+    // rule WEIGHTED: the weights as the device will hold them (rounded to binary32
+    // once in fp32 mode, -0.0 canonicalised), checked after rounding: finite, 0 <= w <= 1, and a
+    // positive weight sum in every row (all summands are >= 0, so the entry-order tree sum is
+    // positive exactly when some weight of the row is)
+    const bool weighted = cfg->rule == ACS_RULE_WEIGHTED;
+    std::vector<double> wsv, wev;
+    if (weighted) {
+        if (!h_wself || !h_wedge) return fail(ACS_EINVAL, "rule WEIGHTED needs acs_create_csr_weighted(w_self, w_edge)");
+        const uint64_t N = cfg->n_nodes;
+        const bool f32 = cfg->dtype == ACS_F32;
+        auto held = [f32](double w) { return (f32 ? (double)(float)w : w) + 0.0; };
+        auto bad = [](double w) { return !(w >= 0.0 && w <= 1.0); };   // (NaN fails both comparisons)
+        wsv.resize(N);
+        wev.resize(csr_nnz);
+        for (uint64_t i = 0; i < N; ++i) {
+            wsv[i] = held(h_wself[i]);
+            if (bad(wsv[i])) return fail(ACS_EINVAL, "w_self[%llu] must be finite, in [0, 1]", (unsigned long long)i);
+            bool pos = wsv[i] > 0.0;
+            for (uint64_t k = h_rowptr[i]; k < h_rowptr[i + 1]; ++k) {
+                wev[k] = held(h_wedge[k]);
+                if (bad(wev[k])) return fail(ACS_EINVAL, "w_edge[%llu] must be finite, in [0, 1]", (unsigned long long)k);
+                pos = pos || wev[k] > 0.0;
+            }
+            if (!pos)
+                return fail(ACS_EINVAL, "receiver %llu: the row's weights sum to 0%s", (unsigned long long)i,
+                            f32 ? " after rounding to binary32" : "");
+        }
+        if (csr_mmax > kGenericMaxM)
+            return fail(ACS_EUNSUPPORTED, "rule WEIGHTED serves rows of at most %u entries (largest row: %llu)",
+                        kGenericMaxM, (unsigned long long)csr_mmax);
     }
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail(ACS_EINVAL, "bad rank / n_ranks");
     const bool partitioned = nranks > 1 || comm_id != nullptr;
@@ -1055,6 +1109,8 @@ static int create_impl(const acs_config* cfg, int device, int nranks, int rank, 
                                               : (uint64_t)cfg->degree + 1;
     s->d = cfg->topology == ACS_TOPO_CSR ? 0 : cfg->degree;
     s->dp = (cfg->degree + 3u) & ~3u;
+    s->weighted = weighted;
+    s->nnz = csr_nnz;
     // "clean": no slot-dependent decision at all (no faults, no loss, no delays)
     s->clean = cfg->fault_model == ACS_FAULT_NONE && drop_threshold(cfg->loss_p) == 0 && cfg->delay_max == 0;
     s->mp.key = key_of(cfg->seed);
@@ -1105,7 +1161,9 @@ static int create_impl(const acs_config* cfg, int device, int nranks, int rank, 
         s->path = PATH_REGULAR;
         s->csr_var = true;
         s->dp = s->d;
-        s->kname = std::string("k_round_regular<") + std::to_string(s->d) + "," + std::to_string(cfg->trim) + ",csr>";
+        s->kname = weighted ? std::string("k_round_weighted<") + std::to_string(s->d) + ",csr>"
+                            : std::string("k_round_regular<") + std::to_string(s->d) + "," +
+                                  std::to_string(cfg->trim) + ",csr>";
     } else if (s->m <= kGenericBigMaxM) {
         s->path = PATH_GENERIC;
         s->generic_small = !(cfg->topology == ACS_TOPO_COMPLETE && s->m > kGenericMaxM);
@@ -1121,7 +1179,8 @@ static int create_impl(const acs_config* cfg, int device, int nranks, int rank, 
         delete s;
         return fail(ACS_EUNSUPPORTED, "fault schedules need N < 2^31");
     }
-    s->ell_sorted = s->path == PATH_REGULAR && s->clean && cfg->rule != ACS_RULE_AVERAGE;
+    s->ell_sorted = s->path == PATH_REGULAR && s->clean && cfg->rule != ACS_RULE_AVERAGE &&
+                    !weighted;   // (WEIGHTED is entry-ordered like AVERAGE, and its weights go by slot)
     const uint64_t rows_local = partitioned ? s->rows_per : s->N;
     // binned exchange (round_binned.hip): one instance, synchronous rounds, and a graph shape with
     // one or two exchange levels (faults and loss are resolved in phase B from tagged values and
@@ -1147,7 +1206,7 @@ static int create_impl(const acs_config* cfg, int device, int nranks, int rank, 
         const bool f32_tags_ok = !s->f32 || s->clean || s->N <= (1ull << 20) || cfg->fault_model != ACS_FAULT_CRASH ||
                                  cfg->n_faulty <= (1u << 20);
         s->binned = allow && f32_tags_ok && s->path == PATH_REGULAR && cfg->delay_max == 0 &&
-                    !(s->csr_var && s->f32) &&
+                    !(s->csr_var && s->f32) && !weighted &&   // (WEIGHTED: per-lane kernel only)
                     // (CSR hub rows own the partial slots after the fast path's blocks; CSR plans
                     // always take kBinSB = kRegularBlock receivers per block, so both paths agree:
                     // static_assert below)
@@ -1339,6 +1398,18 @@ static int create_impl(const acs_config* cfg, int device, int nranks, int rank, 
         CREATE_TRY(hipMalloc(&s->colidx, (csr_nnz ? csr_nnz : 1) * sizeof(uint32_t)));
         CREATE_TRY(hipMemcpy(s->rowptr, h_rowptr, (s->N + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
         if (csr_nnz) CREATE_TRY(hipMemcpy(s->colidx, h_colidx, csr_nnz * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (weighted) {
+            CREATE_TRY(hipMalloc(&s->wself, s->N * s->es));
+            CREATE_TRY(hipMalloc(&s->wedge, (csr_nnz ? csr_nnz : 1) * s->es));
+            if (s->f32) {   // (exact: the values were rounded to binary32 above)
+                std::vector<float> fs(wsv.begin(), wsv.end()), fe(wev.begin(), wev.end());
+                CREATE_TRY(hipMemcpy(s->wself, fs.data(), s->N * sizeof(float), hipMemcpyHostToDevice));
+                if (csr_nnz) CREATE_TRY(hipMemcpy(s->wedge, fe.data(), csr_nnz * sizeof(float), hipMemcpyHostToDevice));
+            } else {
+                CREATE_TRY(hipMemcpy(s->wself, wsv.data(), s->N * sizeof(double), hipMemcpyHostToDevice));
+                if (csr_nnz) CREATE_TRY(hipMemcpy(s->wedge, wev.data(), csr_nnz * sizeof(double), hipMemcpyHostToDevice));
+            }
+        }
         if (s->csr_var) {   // padded ELL (SELL-64 slice widths), sorted rows when order-independent, binned plan
             const uint64_t words = ((s->N + 63) / 64) * 64ull * s->dp;
             CREATE_TRY(hipMalloc(&s->ell, words * sizeof(uint32_t)));
@@ -1347,6 +1418,10 @@ static int create_impl(const acs_config* cfg, int device, int nranks, int rank, 
             CREATE_TRY(hipMemsetAsync(s->ell, 0xFF, words * sizeof(uint32_t), s->stream));
             CREATE_TRY(launch_csr_to_ell(s->rowptr, s->colidx, s->N, s->d, s->ell, s->deg, s->sw, s->stream));
             if (s->ell_sorted) CREATE_TRY(launch_sort_ell_rows(s->ell, s->N, s->d, s->stream));
+            if (weighted) {
+                CREATE_TRY(hipMalloc(&s->well, words * s->es));
+                CREATE_TRY(launch_weights_to_ell(s->rowptr, s->wedge, s->deg, s->N, s->d, s->f32, s->well, s->stream));
+            }
             if (s->binned) {
                 const hipError_t be = binned_build(s->bin, s->ell, bin_desc(s->N), bopt, kBinSB, s->stream);
                 if (be == hipErrorNotSupported) {   // the plan does not fit: the per-lane kernel serves the rows
@@ -1498,7 +1573,41 @@ int acs_create_csr(const acs_config* cfg, const uint64_t* rowptr, const uint32_t
     if (out) *out = nullptr;
     if (!cfg || cfg->topology != ACS_TOPO_CSR) return fail(ACS_EINVAL, "config topology must be ACS_TOPO_CSR");
     if (!rowptr || !colidx) return fail(ACS_EINVAL, "null CSR arrays");
+    if (cfg->rule == ACS_RULE_WEIGHTED)
+        return fail(ACS_EINVAL, "rule WEIGHTED needs weights: use acs_create_csr_weighted");
     return create_impl(cfg, device, 1, 0, nullptr, 0, out, rowptr, colidx);
+}
+
+int acs_create_csr_weighted(const acs_config* cfg, const uint64_t* rowptr, const uint32_t* colidx,
+                            const double* w_self, const double* w_edge, int device, acs_sim** out) {
+    if (out) *out = nullptr;
+    if (!cfg || cfg->topology != ACS_TOPO_CSR) return fail(ACS_EINVAL, "config topology must be ACS_TOPO_CSR");
+    if (cfg->rule != ACS_RULE_WEIGHTED)
+        return fail(ACS_EINVAL, "acs_create_csr_weighted takes rule ACS_RULE_WEIGHTED only (got rule %u)", cfg->rule);
+    if (!rowptr || !colidx) return fail(ACS_EINVAL, "null CSR arrays");
+    if (!w_self || !w_edge) return fail(ACS_EINVAL, "null weight arrays");
+    return create_impl(cfg, device, 1, 0, nullptr, 0, out, rowptr, colidx, w_self, w_edge);
+}
+
+int acs_get_weights(acs_sim* s, double* w_self_out, uint64_t n, double* w_edge_out, uint64_t nnz) {
+    if (!s || !w_self_out || (!w_edge_out && nnz)) return fail(ACS_EINVAL, "null argument");
+    if (!s->weighted) return fail(ACS_EINVAL, "acs_get_weights: not a rule-WEIGHTED handle");
+    if (n != s->N || nnz != s->nnz)
+        return fail(ACS_EINVAL, "acs_get_weights: expected n = %llu, nnz = %llu", (unsigned long long)s->N,
+                    (unsigned long long)s->nnz);
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (s->f32) {
+        std::vector<float> fs(n), fe(nnz);
+        HIP_TRY(hipMemcpy(fs.data(), s->wself, n * sizeof(float), hipMemcpyDeviceToHost));
+        if (nnz) HIP_TRY(hipMemcpy(fe.data(), s->wedge, nnz * sizeof(float), hipMemcpyDeviceToHost));
+        for (uint64_t k = 0; k < n; ++k) w_self_out[k] = fs[k];
+        for (uint64_t k = 0; k < nnz; ++k) w_edge_out[k] = fe[k];
+    } else {
+        HIP_TRY(hipMemcpy(w_self_out, s->wself, n * sizeof(double), hipMemcpyDeviceToHost));
+        if (nnz) HIP_TRY(hipMemcpy(w_edge_out, s->wedge, nnz * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return ACS_OK;
 }
 
 int acs_comm_id_size(void) { return (int)sizeof(ncclUniqueId); }

@@ -7,6 +7,8 @@
 //               groups, u32 [ceil(N/64)][Dp/4][64][4] (Dp = d rounded up to 4): lane l of a
 //               wave loads its 4 neighbour ids of group q with one 16-byte load, and the wave's
 //               64 loads are one contiguous 1 KiB line run
+//   wself, wedge, well : rule WEIGHTED only: per-entry weights of the config dtype,
+//               [N], [nnz] by slot, and the edge weights again in the ELL's own order
 //   status    : u32 [B][N] fault status (§A.4), absent when there are no faults
 //   st        : InstState [B] — honest lo/hi/spread of the current round, rounds, done flags
 //   partial   : double2 [B][nblk] per-block honest (min, max) partials of x^{r+1} (§A.8)
@@ -80,6 +82,13 @@ struct RoundArgs {
     // narrow stage (binned phase B of narrow plans): {base lo, base hi, entry
     // width 4 or 8, 0}, written by this round's phase A (BinnedPlan::nhdr; launch_round_binned sets it)
     const uint4* nhdr;
+    // rule WEIGHTED (CSR only), values of the config dtype: wself[i] weighs entry 0,
+    // wedge[slot] entry 1+t (the generic kernel reads these two), and well holds the edge weights of
+    // the fast path's rows in the ELL's own slice / group / lane order, [ceil(N/64)][d/4][64][4]
+    // (+0.0 in absent columns), so a wave's weight loads are contiguous like its id loads
+    const void* wself;
+    const void* wedge;
+    const void* well;
 };
 constexpr uint32_t kEaccSlots = 32, kEaccStride = 16;       // eacc pairs, u64 words between pairs
 constexpr uint32_t kEaccWords = kEaccSlots * kEaccStride;   // eacc words of one round parity
@@ -173,6 +182,15 @@ bool regular_fast_supported(uint32_t d, uint32_t t, uint32_t rule);
 const char* regular_fast_name(uint32_t d, uint32_t t, bool clean);
 hipError_t launch_round_regular(const RoundArgs& a, uint64_t B, bool clean, hipStream_t s);
 constexpr uint32_t kRegularBlock = 256;
+
+// Rule WEIGHTED on a CSR graph (round_weighted.hip): one lane per receiver over the padded ELL of
+// width d in {4, 8, 16, 32} and the weight array beside it; hub rows (kDegHub) are skipped.
+bool weighted_fast_supported(uint32_t d);
+// nblk_fast: the kernel's own blocks (kRegularBlock rows each; hub rows' partial slots follow them)
+hipError_t launch_round_weighted(const RoundArgs& a, uint64_t B, uint32_t nblk_fast, hipStream_t s);
+// wedge (CSR slot order) -> well (the ELL's order) for the rows deg[] does not mark as hubs
+hipError_t launch_weights_to_ell(const uint64_t* rowptr, const void* wedge, const uint8_t* deg, uint64_t N,
+                                 uint32_t d, bool f32, void* well, hipStream_t s);
 
 // Binned exchange (round_binned.hip): the one-instance RANDOM_REGULAR round as streaming kernels
 // instead of N·d random 8-byte gathers (clean, lossy and faulty configs; no delays).  Deliveries (i <- j) are grouped into

@@ -174,6 +174,35 @@ __global__ __launch_bounds__(BLK) void k_round_generic(const RoundArgs a, uint32
     while (P < m) P <<= 1;
     const VT lo = (VT)S->lo, hi = (VT)S->hi;
     const bool avg = a.rule == 0;
+    if (a.rule == 5) {
+        // WEIGHTED (CSR rows): products p_e = (w_e * v_e) + 0.0 in one LDS half, weights
+        // in the other, one entry-order tree sum each; an entry OMIT leaves out (and the padding
+        // past m) adds +0.0 to both.  A zero weight sum (OMIT only) keeps x_i.
+        const VT* __restrict__ ws = reinterpret_cast<const VT*>(a.wself);
+        const VT* __restrict__ we = reinterpret_cast<const VT*>(a.wedge);
+        for (uint32_t e = threadIdx.x; e < P; e += BLK) {
+            VT pe = VT(0), wt = VT(0);
+            if (e < m) {
+                bool out;
+                const VT v = generic_entry<VT>(a, lb, b, bG, i, rp, e, x, stv, xi, lo, hi, out);
+                if (!out) {
+                    wt = e == 0 ? ws[i] : we[rp + e - 1];
+                    pe = wt * v + VT(0);
+                }
+            }
+            sh[e] = pe;
+            sh[P + e] = wt;
+        }
+        __syncthreads();
+        const VT num = block_tree_sum<BLK>(sh, P);
+        const VT den = block_tree_sum<BLK>(sh + P, P);
+        if (threadIdx.x == 0) {
+            const VT res = den > VT(0) ? num / den : xi;
+            xo[i] = res;
+            *part = honest ? make_double2((double)res, (double)res) : make_double2(kInf, -kInf);
+        }
+        return;
+    }
     __shared__ uint32_t nmiss_s;   // entries left out under missing_policy = OMIT
     if (threadIdx.x == 0) nmiss_s = 0;
     __syncthreads();

@@ -1,0 +1,187 @@
+// round_weighted.hip — rule WEIGHTED: edge-weighted averaging x' = W x on a CSR graph.
+//
+// One lane = one receiver i of a CSR graph padded to a compile-time width D (the SELL-64 ELL of the
+// CSR register path: column groups past the slice's widest row are not loaded, columns past deg(i)
+// are absent entries).  Per lane and round:
+//   - D/4 coalesced 16-byte loads of sender ids and, beside them, the same groups of the weight
+//     array (same slice / group / lane order: 16 B per lane in fp32, 32 B in fp64, contiguous over
+//     the wave);
+//   - the x gathers (and status gathers) of every present column, issued together before any resolve;
+//   - §A.6 resolution, one DROP draw per slot (CSR slots rowptr[i] + t are not 4-aligned);
+//   - p_e = (w_e * v_e) + 0.0 (two roundings, no FMA: -ffp-contract=off) and the two §A.7 tree sums
+//     over the m = D + 1 entries in entry order, in registers; absent columns and (OMIT) missing
+//     entries add +0.0 to both;
+//   - one IEEE divide (x_i is kept when the weight sum is 0, which only OMIT can produce), one store;
+//   - honest (min, max) of x^{r+1} reduced per block -> one partial (§A.8 epilogue).
+// Hub rows (deg[i] = kDegHub) are left to k_round_generic's rule-5 branch.
+#include "resolve.hpp"
+#include "rules.hpp"
+
+namespace acs {
+
+template <typename VT>
+struct WVec4;
+template <>
+struct WVec4<float> {
+    using type = float4;
+};
+template <>
+struct WVec4<double> {
+    using type = double4;
+};
+
+template <int D, typename VT>
+__global__ __launch_bounds__(kRegularBlock) void k_round_weighted(const RoundArgs a) {
+    static_assert(D % 4 == 0, "compiled widths are multiples of 4");
+    constexpr int M = D + 1;
+    constexpr int NQ = D / 4;
+    using W4 = typename WVec4<VT>::type;
+    const uint32_t lb = blockIdx.y;
+    InstState* S = a.st + lb;
+    if (S->done) return;  // device-side early exit (uniform per block)
+
+    const uint64_t N = a.N;
+    const VT* __restrict__ x = reinterpret_cast<const VT*>(a.xin) + lb * N;
+    VT* __restrict__ xo = reinterpret_cast<VT*>(a.xout) + lb * N;
+    const uint32_t i = blockIdx.x * kRegularBlock + threadIdx.x;   // receiver = ELL row
+
+    double mn = kInf, mx = -kInf;   // exact for binary32 values too
+    if (i < N && a.deg[i] != kDegHub) {
+        const VT xi = x[i];
+        VT res = xi;
+        bool honest = true, active = true;
+        const uint32_t* stv = nullptr;   // null: no fault schedule
+        if (a.status) {
+            stv = a.status + lb * N;
+            const uint32_t si = stv[i];
+            honest = si == kHonest;
+            active = is_active(si, a.r);
+        }
+        if (active) {
+            const uint64_t g0 = (uint64_t)(i >> 6) * (NQ * 64) + (i & 63);
+            const uint4* cp = reinterpret_cast<const uint4*>(a.ell) + g0;
+            const W4* wp = reinterpret_cast<const W4*>(a.well) + g0;
+            const uint32_t nqs = a.sw[i >> 6];   // uniform over the wave (one 64-row slice)
+            const uint32_t dg = a.deg[i];
+            const uint64_t rp = a.rowptr[i];
+            uint32_t col[D];
+            VT w[M], p[M];
+            w[0] = reinterpret_cast<const VT*>(a.wself)[i];
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                uint4 c = make_uint4(kEllNone, kEllNone, kEllNone, kEllNone);
+                W4 ww;
+                ww.x = ww.y = ww.z = ww.w = VT(0);
+                if ((uint32_t)q < nqs) {   // groups past the slice's width are not loaded
+                    c = cp[q * 64];
+                    ww = wp[q * 64];
+                }
+                col[4 * q + 0] = c.x;
+                col[4 * q + 1] = c.y;
+                col[4 * q + 2] = c.z;
+                col[4 * q + 3] = c.w;
+                w[1 + 4 * q + 0] = ww.x;
+                w[1 + 4 * q + 1] = ww.y;
+                w[1 + 4 * q + 2] = ww.z;
+                w[1 + 4 * q + 3] = ww.w;
+            }
+            const MsgParams& mp = a.mp;
+            const uint32_t b = (uint32_t)(mp.inst_offset + lb);
+            const uint32_t bG = b - b % mp.mask_group;
+            const VT lo = (VT)S->lo, hi = (VT)S->hi;
+            const uint32_t r = a.r;
+            VT xj[D];
+            uint32_t sj[D];
+            // all gathers first; absent columns load nothing
+#pragma unroll
+            for (int t = 0; t < D; ++t) {
+                const bool ok = (uint32_t)t < dg;
+                const uint32_t j = ok ? col[t] : i;
+                if (a.delay)
+                    xj[t] = ok ? delayed_x<VT>(a, lb, r, draw(mp.key, kStreamDelay, b, r, rp + t), j) : xi;
+                else
+                    xj[t] = ok ? x[j] : xi;
+                sj[t] = (ok && stv) ? stv[j] : kHonest;
+            }
+            p[0] = w[0] * xi + VT(0);
+#pragma unroll
+            for (int t = 0; t < D; ++t) {
+                bool gone = (uint32_t)t >= dg;   // absent column: +0.0 in both sums (w is +0.0 already)
+                VT u = xi;
+                if (!gone) {
+                    const uint64_t s = rp + t;
+                    const bool dropped = mp.thr && draw(mp.key, kStreamDrop, bG, r, s) < mp.thr;
+                    bool miss;
+                    u = resolve_entry_m(mp, sj[t], xj[t], xi, dropped, b, r, i, s, lo, hi, miss);
+                    gone = mp.omit && miss;   // SELF: the entry takes x_i and keeps its weight
+                }
+                const VT wt = gone ? VT(0) : w[1 + t];
+                w[1 + t] = wt;
+                p[1 + t] = gone ? VT(0) : wt * u + VT(0);
+            }
+            const VT num = tree_sum_const<M>(p), den = tree_sum_const<M>(w);
+            if (den > VT(0)) res = num / den;   // den = 0: every present weight is 0 (OMIT) -> keep x_i
+        }
+        xo[i] = res;
+        if (honest) {
+            mn = res;
+            mx = res;
+        }
+    }
+    block_minmax_store<kRegularBlock>(mn, mx, a.partial + (uint64_t)lb * a.nblk + blockIdx.x);
+}
+
+// wedge (slot order) -> the ELL's slice / group / lane order, +0.0 in absent columns; hub rows keep
+// an all-zero row (the fast kernel never reads it)
+template <typename VT>
+__global__ __launch_bounds__(256) void k_weights_to_ell(const uint64_t* __restrict__ rowptr, const VT* __restrict__ wedge,
+                                                        const uint8_t* __restrict__ deg, uint64_t N, uint32_t d,
+                                                        VT* __restrict__ well) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const uint64_t rp = rowptr[i];
+    const uint32_t dg = deg[i] == kDegHub ? 0u : deg[i];
+    for (uint32_t t = 0; t < d; ++t)
+        well[(((i >> 6) * (d >> 2) + (t >> 2)) * 64 + (i & 63)) * 4 + (t & 3)] = t < dg ? wedge[rp + t] : VT(0);
+}
+
+hipError_t launch_weights_to_ell(const uint64_t* rowptr, const void* wedge, const uint8_t* deg, uint64_t N,
+                                 uint32_t d, bool f32, void* well, hipStream_t s) {
+    const dim3 grid((unsigned)((N + 255) / 256));
+    if (f32)
+        hipLaunchKernelGGL(k_weights_to_ell<float>, grid, dim3(256), 0, s, rowptr, static_cast<const float*>(wedge), deg,
+                           N, d, static_cast<float*>(well));
+    else
+        hipLaunchKernelGGL(k_weights_to_ell<double>, grid, dim3(256), 0, s, rowptr, static_cast<const double*>(wedge),
+                           deg, N, d, static_cast<double*>(well));
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------- dispatch
+#define ACS_WEIGHTED_WIDTHS(X) X(4) X(8) X(16) X(32)
+
+bool weighted_fast_supported(uint32_t d) {
+#define X(DD) if (d == DD) return true;
+    ACS_WEIGHTED_WIDTHS(X)
+#undef X
+    return false;
+}
+
+hipError_t launch_round_weighted(const RoundArgs& a, uint64_t B, uint32_t nblk_fast, hipStream_t s) {
+    if (!a.deg || !a.sw || !a.ell || !a.well || !a.wself || !a.rowptr) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)nblk_fast, (unsigned)B);
+    const dim3 block(kRegularBlock);
+#define X(DD)                                                                        \
+    if (a.d == DD) {                                                                 \
+        if (a.f32)                                                                   \
+            hipLaunchKernelGGL((k_round_weighted<DD, float>), grid, block, 0, s, a);  \
+        else                                                                         \
+            hipLaunchKernelGGL((k_round_weighted<DD, double>), grid, block, 0, s, a); \
+        return hipGetLastError();                                                    \
+    }
+    ACS_WEIGHTED_WIDTHS(X)
+#undef X
+    return hipErrorNotSupported;
+}
+
+}  // namespace acs

@@ -25,8 +25,9 @@
 extern "C" {
 #endif
 
-#define ACS_ABI_VERSION 3   /* 2: acs_config.delay_max (bounded-delay rounds);
-                               3: acs_config.missing_policy (was reserved0), acs_get_all_values */
+#define ACS_ABI_VERSION 4   /* 2: acs_config.delay_max (bounded-delay rounds);
+                               3: acs_config.missing_policy (was reserved0), acs_get_all_values;
+                               4: ACS_RULE_WEIGHTED, acs_create_csr_weighted, acs_get_weights */
 
 /* status codes */
 #define ACS_OK            0
@@ -55,6 +56,10 @@ extern "C" {
 /* W-MSR (LeBlanc et al. 2013): drop up to t entries strictly below the receiver's
  * own value (the smallest ones) and up to t strictly above it (the largest), average the rest */
 #define ACS_RULE_WMSR          4
+/* Edge-weighted averaging x' = W x on a CSR graph: entry e of receiver i carries a
+ * weight (w_self[i], then w_edge[slot]); x_i' = tree_sum(w_e * v_e) / tree_sum(w_e).  CSR topology
+ * and trim == 0 only; handles come from acs_create_csr_weighted */
+#define ACS_RULE_WEIGHTED      5
 
 /* fault model (§A.4) */
 #define ACS_FAULT_NONE       0
@@ -157,6 +162,20 @@ int acs_create(const acs_config* cfg, int backend, const int* devices, int n_dev
  * Both arrays are copied to the device. */
 int acs_create_csr(const acs_config* cfg, const uint64_t* rowptr, const uint32_t* colidx, int device,
                    struct acs_sim** out);
+
+/* DESIGN.md §9 (rule "weighted"): acs_create_csr with one weight per entry, shared by all
+ * instances: w_self[N] for entry 0 and w_edge[rowptr[N]] indexed by slot.  cfg->rule must be
+ * ACS_RULE_WEIGHTED (and only this entry point takes that rule) with cfg->trim == 0.  Every weight
+ * must be finite with 0 <= w <= 1 and every row's weight sum positive; with cfg->dtype = ACS_F32
+ * the weights are rounded to binary32 once, here, and checked after rounding.  All of this is
+ * checked on the host before any device call (ACS_EINVAL).  Rows above 8192 entries are not
+ * served yet (ACS_EUNSUPPORTED). */
+int acs_create_csr_weighted(const acs_config* cfg, const uint64_t* rowptr, const uint32_t* colidx,
+                            const double* w_self, const double* w_edge, int device, struct acs_sim** out);
+
+/* The weights the device holds (fp32 handles: the rounded weights, widened back to double):
+ * n = N values into w_self_out, nnz = rowptr[N] values into w_edge_out.  Weighted handles only. */
+int acs_get_weights(struct acs_sim* sim, double* w_self_out, uint64_t n, double* w_edge_out, uint64_t nnz);
 
 /* §8(e) node partitioning of ONE RANDOM_REGULAR instance over n_ranks GPUs (cfg5), one process
  * (or thread) per GPU.  Rank r owns the 64-aligned row block [r*R, (r+1)*R) ∩ [0, N),
