@@ -7,6 +7,8 @@
   python -m acsim run --preset cfg4 --graph my_graph.npz --set trim=2 ...   (user CSR graph,
       acsim or scipy.sparse .npz layout; topology and n_nodes come from the file)
   python -m acsim run --graph weighted.npz --set rule=weighted ...   (the file's weights too)
+  python -m acsim run --graph directed.npz --set rule=pushsum ...   (the file's weights when it has
+      them, else graphs.pushsum_weights; the choice is reported on stderr)
 """
 from __future__ import annotations
 
@@ -106,6 +108,19 @@ def main(argv=None) -> int:
         if _enum("rule", cfg.rule) == _abi.RULE_WEIGHTED:   # the file's weights go with the rule
             g = load_csr(a.graph, weights=True)
             csr, weights = g[:2], g[2:]
+        elif _enum("rule", cfg.rule) == _abi.RULE_PUSHSUM:   # the file's weights, else 1 / (outdeg + 1)
+            from .graphs import pushsum_weights
+            try:
+                g = load_csr(a.graph, weights=True)
+                csr, weights = g[:2], g[2:]
+                print(f"pushsum: using the weights of {a.graph}", file=sys.stderr)
+            except ValueError as e:
+                if "no weights" not in str(e):
+                    raise
+                csr = load_csr(a.graph)
+                weights = pushsum_weights(*csr, dtype=cfg.dtype)
+                print(f"pushsum: {a.graph} has no weights, using graphs.pushsum_weights (1 / (outdeg + 1))",
+                      file=sys.stderr)
         else:
             csr = load_csr(a.graph)
         cfg = cfg.replace(topology="csr", n_nodes=int(csr[0].size - 1))

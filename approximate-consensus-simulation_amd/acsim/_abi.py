@@ -21,6 +21,7 @@ BACKEND_CPU, BACKEND_HIP = 0, 1
 # topology / rule / faults / byz / termination / dtype
 TOPO_COMPLETE, TOPO_RANDOM_REGULAR, TOPO_CSR = 0, 1, 2
 RULE_AVERAGE, RULE_TRIMMED_MEAN, RULE_MIDPOINT, RULE_DLPSW_SELECT, RULE_WMSR, RULE_WEIGHTED = 0, 1, 2, 3, 4, 5
+RULE_PUSHSUM = 6
 FAULT_NONE, FAULT_CRASH, FAULT_BYZANTINE = 0, 1, 2
 BYZ_SPLIT, BYZ_RANDOM, BYZ_CONSTANT = 0, 1, 2
 TERM_EPS, TERM_FIXED = 0, 1
@@ -126,6 +127,8 @@ def _declare(lib: C.CDLL) -> None:
         "acs_get_instance_spread": (i32, [vp, P(C.c_double), u64]),
         "acs_get_spread_trace": (i32, [vp, u64, P(C.c_double), u64, P(u64)]),
         "acs_set_state": (i32, [vp, u32, vp, u64]),
+        "acs_get_pushsum_state": (i32, [vp, u64, vp, vp, u64]),
+        "acs_set_pushsum_state": (i32, [vp, u32, vp, vp, u64]),
         "acs_get_fault_status": (i32, [vp, P(u32), u64]),
         "acs_get_neighbors": (i32, [vp, P(u32), u64]),
         "acs_set_kernel_timing": (i32, [vp, i32]),

@@ -1,6 +1,6 @@
 """Synthetic user graphs in CSR form for the ACS_TOPO_CSR topology:
 ``(rowptr uint64[N+1], colidx uint32[nnz])`` as ``acsim.Simulator(cfg, csr=...)`` takes them,
-and the edge weights of rule "weighted" (``weights=(w_self, w_edge)``).
+and the edge weights of rules "weighted" and "pushsum" (``weights=(w_self, w_edge)``).
 Used by the CSR benchmarks and tests; any CSR the caller builds works the same way."""
 from __future__ import annotations
 
@@ -112,6 +112,38 @@ def metropolis_weights(rowptr, colidx):
     we = 1.0 / (1.0 + np.maximum(deg[rows], deg[ci.astype(np.int64)]).astype(np.float64))
     ws = 1.0 - np.bincount(rows, weights=we, minlength=deg.size)
     return ws, we
+
+
+def pushsum_weights(rowptr, colidx, dtype="f64"):
+    """Push-sum weights of a directed graph (rule "pushsum"): sender j gives
+    1 / (outdeg(j) + 1) to itself and to each slot it appears on (outdeg(j) = its slots in colidx), so
+    every column of W sums to 1 and the mass sum(s) / sum(z) is the mean of x^0.  Where
+    (outdeg + 1) times the rounded weight exceeds 1 exactly, the weight is taken one ulp lower, so
+    every exact column sum is at most 1.  dtype="f32" (a Config's dtype) rounds and steps in
+    binary32, for a handle that holds binary32 weights: rounding float64 weights there would push
+    half the columns above 1.  Returns (w_self, w_edge) as float64."""
+    rp, ci = check_csr(rowptr, colidx)
+    ft, p = (np.float32, 24) if str(dtype) in ("f32", "float32") else (np.float64, 53)
+    k = np.bincount(ci.astype(np.int64), minlength=rp.size - 1).astype(np.int64) + 1
+    w = (ft(1) / k.astype(ft)).astype(ft)
+    # k * w > 1, decided exactly in integers: w = mi * 2^(e - p) with mi = the p-bit significand
+    m, e = np.frexp(w.astype(np.float64))
+    mi = np.ldexp(m, p).astype(np.int64).astype(object) * k.astype(object)   # exact integers
+    over = np.array([int(a) > (1 << int(p - b)) for a, b in zip(mi, e)], dtype=bool)
+    w = np.where(over, np.nextafter(w, ft(0)), w).astype(np.float64)
+    return w.copy(), w[ci.astype(np.int64)]
+
+
+def column_sums(rowptr, colidx, w_self, w_edge):
+    """Column sums of the weight matrix: w_self[j] plus every w_edge[slot] with colidx[slot] == j,
+    each as a correctly rounded sum (math.fsum).  Rule "pushsum" needs every one <= 1 + 2^-30."""
+    import math
+    rp, ci = check_csr(rowptr, colidx)
+    ws, we = check_weights(rp, w_self, w_edge)
+    order = np.argsort(ci, kind="stable")
+    start = np.concatenate([[0], np.cumsum(np.bincount(ci.astype(np.int64), minlength=ws.size))])
+    wo = we[order]
+    return np.array([math.fsum([ws[j]] + wo[start[j]:start[j + 1]].tolist()) for j in range(ws.size)])
 
 
 def scale_weights(w_self, w_edge):

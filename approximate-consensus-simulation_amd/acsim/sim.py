@@ -50,8 +50,9 @@ class Simulator:
         `device`; without it all partitions are simulated on `device` with private x copies
         (validation mode, see include/acsim.h acs_create_partitioned).
 
-        weights = (w_self[N], w_edge[nnz]) with csr and rule="weighted" (DESIGN.md §9): receiver
-        i's own entry weighs w_self[i], the message on slot s weighs w_edge[s]."""
+        weights = (w_self[N], w_edge[nnz]) with csr and rule="weighted" or rule="pushsum"
+        (DESIGN.md §9): receiver i's own entry weighs w_self[i], the message on slot s weighs
+        w_edge[s].  For "pushsum" the column sums must not exceed 1 (graphs.pushsum_weights)."""
         if isinstance(cfg, str):
             cfg = preset(cfg)
         if backend != "hip":
@@ -64,7 +65,7 @@ class Simulator:
         h = C.c_void_p()
         if weights is not None and csr is None:
             raise ValueError("weights need a csr graph")
-        if csr is not None and weights is not None:   # rule="weighted" (acs_create_csr_weighted)
+        if csr is not None and weights is not None:   # rule="weighted" / "pushsum" (acs_create_csr_weighted)
             rp = np.ascontiguousarray(csr[0], dtype=np.uint64)
             ci = np.ascontiguousarray(csr[1], dtype=np.uint32)
             ws = np.ascontiguousarray(weights[0], dtype=np.float64)
@@ -198,6 +199,28 @@ class Simulator:
         x = np.ascontiguousarray(xv, dtype=self.value_dtype).reshape(-1)
         self._chk(self._lib.acs_set_state(self._h, int(round), x.ctypes.data, x.size))
 
+    def pushsum_state(self, instance: int = 0):
+        """(s[N], z[N]) of one instance (rule="pushsum"); values() is s / z."""
+        s = np.empty(self.N, dtype=self.value_dtype)
+        z = np.empty(self.N, dtype=self.value_dtype)
+        self._chk(self._lib.acs_get_pushsum_state(self._h, int(instance), s.ctypes.data, z.ctypes.data, s.size))
+        return s, z
+
+    def set_pushsum_state(self, round: int, s: np.ndarray, z: np.ndarray) -> None:
+        """Resume a rule="pushsum" handle at `round` with the pairs (s, z), B*N values each
+        (instance-major); x becomes s / z where z > 0 and s where z = 0."""
+        arrs = []
+        for v in (s, z):
+            v = np.asarray(v)
+            if self.value_dtype == np.float32 and v.dtype != np.float32 and not np.array_equal(
+                    v.astype(np.float32).astype(v.dtype), v):
+                raise ValueError("fp32 set_pushsum_state: values must be exactly representable in binary32")
+            arrs.append(np.ascontiguousarray(v, dtype=self.value_dtype).reshape(-1))
+        if arrs[0].size != arrs[1].size:
+            raise ValueError("s and z must have the same size")
+        self._chk(self._lib.acs_set_pushsum_state(self._h, int(round), arrs[0].ctypes.data, arrs[1].ctypes.data,
+                                                  arrs[0].size))
+
     def fault_status(self) -> np.ndarray:
         out = np.empty(self.B * self.N, dtype=np.uint32)
         self._chk(self._lib.acs_get_fault_status(
@@ -205,7 +228,7 @@ class Simulator:
         return out.reshape(self.B, self.N)
 
     def weights(self):
-        """(w_self[N], w_edge[nnz]) as the device holds them (rule="weighted"; with dtype="f32" the
+        """(w_self[N], w_edge[nnz]) as the device holds them (rule="weighted" / "pushsum"; with dtype="f32" the
         weights rounded to binary32, returned as float64)."""
         ws = np.empty(self.N, dtype=np.float64)
         we = np.empty(getattr(self, "_nnz", 0), dtype=np.float64)

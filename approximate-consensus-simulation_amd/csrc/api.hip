@@ -152,6 +152,10 @@ struct acs_sim {
     void* wself = nullptr;         // [N]
     void* wedge = nullptr;         // [nnz] slot order (generic kernel, acs_get_weights)
     void* well = nullptr;          // the ELL's order (csr_var; RoundArgs::well)
+    // rule PUSHSUM (a weighted handle too): (s, z) pairs of the config dtype beside x,
+    // two buffers [B][N]; instance b at round r lives in buffer r & 1
+    bool pushsum = false;
+    void* pairs = nullptr;
     double* dsorted = nullptr;     // dense path: sorted base multiset [N]
     uint32_t* dcounts = nullptr;   // dense path: |B|, #Byzantine, #crash-silent
     std::vector<Part> parts;       // virtual partitions 1..P-1 (partition 0 uses x / ell)
@@ -168,6 +172,13 @@ struct acs_sim {
     uint64_t timed_launches = 0;
     std::string kname;
 };
+
+// Rule PUSHSUM ("mass bound"): column sums at most 1 + 2^-30, admitted |s| and the
+// fp32 round limit, chosen together so that no sum of a run can overflow.
+static constexpr double kPushsumColMax = 1.0 + 0x1p-30;
+static constexpr double kPushsumMaxAbs64 = 1e290;
+static constexpr float kPushsumMaxAbs32 = 1e26f;
+static constexpr uint32_t kPushsumF32MaxRounds = 1u << 22;
 
 // ------------------------------------------------------------------------- validation
 // §A.8 constraints (restated here independently of the oracle's copy).
@@ -196,9 +207,10 @@ static int validate(const acs_config* c) {
     }
     if (slots >= (1ull << 34)) return fail(ACS_EINVAL, "slot count must be < 2^34");
     if (c->topology == ACS_TOPO_CSR) {
-        if (c->rule > ACS_RULE_WEIGHTED) return fail(ACS_EINVAL, "unknown rule %u", c->rule);
+        if (c->rule > ACS_RULE_PUSHSUM) return fail(ACS_EINVAL, "unknown rule %u", c->rule);
         if (c->rule == ACS_RULE_AVERAGE && c->trim != 0) return fail(ACS_EINVAL, "AVERAGE requires trim == 0");
         if (c->rule == ACS_RULE_WEIGHTED && c->trim != 0) return fail(ACS_EINVAL, "WEIGHTED requires trim == 0");
+        if (c->rule == ACS_RULE_PUSHSUM && c->trim != 0) return fail(ACS_EINVAL, "PUSHSUM requires trim == 0");
         if (c->rule == ACS_RULE_DLPSW_SELECT && c->trim < 1) return fail(ACS_EINVAL, "DLPSW needs t >= 1");
     } else
     switch (c->rule) {
@@ -215,6 +227,8 @@ static int validate(const acs_config* c) {
             break;
         case ACS_RULE_WEIGHTED:
             return fail(ACS_EINVAL, "WEIGHTED needs a CSR graph with weights: use acs_create_csr_weighted");
+        case ACS_RULE_PUSHSUM:
+            return fail(ACS_EINVAL, "PUSHSUM needs a CSR graph with weights: use acs_create_csr_weighted");
         default:
             return fail(ACS_EINVAL, "unknown rule %u", c->rule);
     }
@@ -246,6 +260,17 @@ static int validate(const acs_config* c) {
     if (c->missing_policy > ACS_MISSING_OMIT) return fail(ACS_EINVAL, "unknown missing_policy %u", c->missing_policy);
     if (c->trace_spread && c->n_instances * ((uint64_t)c->max_rounds + 1) > (1ull << 28))
         return fail(ACS_EINVAL, "spread trace too large (B*(max_rounds+1) > 2^28)");
+    if (c->rule == ACS_RULE_PUSHSUM) {
+        if (c->fault_model != ACS_FAULT_NONE)
+            return fail(ACS_EINVAL, "PUSHSUM is not defined under faults: Byzantine and crash values are "
+                                    "defined on x, not on (s, z) pairs");
+        if (c->loss_p > 0.0 && c->missing_policy != ACS_MISSING_OMIT)
+            return fail(ACS_EINVAL, "PUSHSUM with loss_p > 0 needs missing_policy = OMIT: SELF would put the "
+                                    "receiver's own pair in place of a lost message and create mass");
+        if (c->delay_max > 0) return fail(ACS_EUNSUPPORTED, "PUSHSUM does not serve delay_max > 0 yet");
+        if (c->dtype == ACS_F32 && c->max_rounds > kPushsumF32MaxRounds)
+            return fail(ACS_EINVAL, "PUSHSUM in fp32 needs max_rounds <= 2^22 (binary32 sums stay finite, DESIGN.md §9)");
+    }
     return ACS_OK;
 }
 
@@ -329,6 +354,7 @@ static void release(acs_sim* s) {
     (void)hipFree(s->wself);
     (void)hipFree(s->wedge);
     (void)hipFree(s->well);
+    (void)hipFree(s->pairs);
     (void)hipFree(s->gen_ids);
     (void)hipFree(s->crank);
     (void)hipFree(s->clist);
@@ -353,6 +379,11 @@ static double* xb(const acs_sim* s, uint32_t q) {
 // element k of a value buffer (byte arithmetic on the config's value size)
 static void* xat(const acs_sim* s, const void* base, uint64_t k) {
     return const_cast<char*>(static_cast<const char*>(base)) + k * s->es;
+}
+
+// rule PUSHSUM: the pair buffer of round q (parity q & 1; synchronous rounds only)
+static void* pairs_at(const acs_sim* s, uint32_t q) {
+    return static_cast<char*>(s->pairs) + (uint64_t)(q & 1u) * s->B * s->N * 2 * s->es;
 }
 
 static FinalizeArgs make_finalize(acs_sim* s, uint32_t r_next, const double2* partial, uint32_t nblk,
@@ -505,6 +536,10 @@ static RoundArgs round_args(acs_sim* s, uint32_t r) {
     a.wself = s->wself;
     a.wedge = s->wedge;
     a.well = s->well;
+    if (s->pushsum) {
+        a.pin = pairs_at(s, r);
+        a.pout = pairs_at(s, r + 1);
+    }
     return a;
 }
 
@@ -647,6 +682,8 @@ static int enqueue_round(acs_sim* s, uint32_t r) {
             if (s->n_hub) ab.qhi = s->nblk_fast;   // the hub rows' partial slots are the generic kernel's
             HIP_TRY(launch_round_binned(s->bin, ab, s->clean, s->stream, s->fin_pending ? &s->fin_args : nullptr));
             s->fin_pending = false;
+        } else if (s->path == PATH_REGULAR && s->pushsum) {
+            HIP_TRY(launch_round_pushsum(a, s->B, s->nblk_fast, s->stream));
         } else if (s->path == PATH_REGULAR && s->weighted) {
             HIP_TRY(launch_round_weighted(a, s->B, s->nblk_fast, s->stream));
         } else if (s->path == PATH_REGULAR) {
@@ -980,9 +1017,12 @@ static int advance(acs_sim* s, uint32_t k) {
 
 // CSR on the register / binned paths (§8(f) row 1): the smallest compiled degree D >= the
 // largest row with the config's (t, rule), 0 if none (the generic kernel then runs).
-// (rule WEIGHTED has its own per-lane kernel, k_round_weighted<D>, over the same padded rows)
+// (rules WEIGHTED and PUSHSUM have their own per-lane kernels, k_round_weighted<D> and
+// k_round_pushsum<D>, over the same padded rows)
 static bool csr_width_compiled(uint32_t d, uint32_t t, uint32_t rule) {
-    return rule == ACS_RULE_WEIGHTED ? t == 0 && weighted_fast_supported(d) : regular_fast_supported(d, t, rule);
+    if (rule == ACS_RULE_WEIGHTED) return t == 0 && weighted_fast_supported(d);
+    if (rule == ACS_RULE_PUSHSUM) return t == 0 && pushsum_fast_supported(d);
+    return regular_fast_supported(d, t, rule);
 }
 
 static uint32_t csr_fast_degree(uint64_t maxdeg, uint32_t t, uint32_t rule) {
@@ -1053,7 +1093,8 @@ static int create_impl(const acs_config* cfg, int device, int nranks, int rank, 
     // once in fp32 mode, -0.0 canonicalised), checked after rounding: finite, 0 <= w <= 1, and a
     // positive weight sum in every row (all summands are >= 0, so the entry-order tree sum is
     // positive exactly when some weight of the row is)
-    const bool weighted = cfg->rule == ACS_RULE_WEIGHTED;
+    const bool pushsum = cfg->rule == ACS_RULE_PUSHSUM;   // (weights as for WEIGHTED, one more rule below)
+    const bool weighted = cfg->rule == ACS_RULE_WEIGHTED || pushsum;
     std::vector<double> wsv, wev;
     if (weighted) {
         if (!h_wself || !h_wedge) return fail(ACS_EINVAL, "rule WEIGHTED needs acs_create_csr_weighted(w_self, w_edge)");
@@ -1076,9 +1117,26 @@ static int create_impl(const acs_config* cfg, int device, int nranks, int rank, 
                 return fail(ACS_EINVAL, "receiver %llu: the row's weights sum to 0%s", (unsigned long long)i,
                             f32 ? " after rounding to binary32" : "");
         }
+        if (pushsum) {
+            // every column sum <= 1 + 2^-30 (the mass bound of DESIGN.md §9): w_self[j] plus every
+            // w_edge[slot] with colidx[slot] == j, as a compensated (Kahan) double sum, whose error
+            // (about 2 ulps) does not grow with the out-degree
+            std::vector<double> cs(wsv), cc(N, 0.0);
+            for (uint64_t k = 0; k < csr_nnz; ++k) {
+                const uint32_t j = h_colidx[k];
+                const double y = wev[k] - cc[j];   // (no fast-math in this build: the compensation stays)
+                const double tt = cs[j] + y;
+                cc[j] = (tt - cs[j]) - y;
+                cs[j] = tt;
+            }
+            for (uint64_t j = 0; j < N; ++j)
+                if (!(cs[j] <= kPushsumColMax))
+                    return fail(ACS_EINVAL, "sender %llu: column sum %.17g > 1 + 2^-30%s (PUSHSUM must not create mass)",
+                                (unsigned long long)j, cs[j], f32 ? " after rounding to binary32" : "");
+        }
         if (csr_mmax > kGenericMaxM)
-            return fail(ACS_EUNSUPPORTED, "rule WEIGHTED serves rows of at most %u entries (largest row: %llu)",
-                        kGenericMaxM, (unsigned long long)csr_mmax);
+            return fail(ACS_EUNSUPPORTED, "rule %s serves rows of at most %u entries (largest row: %llu)",
+                        pushsum ? "PUSHSUM" : "WEIGHTED", kGenericMaxM, (unsigned long long)csr_mmax);
     }
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail(ACS_EINVAL, "bad rank / n_ranks");
     const bool partitioned = nranks > 1 || comm_id != nullptr;
@@ -1110,6 +1168,7 @@ static int create_impl(const acs_config* cfg, int device, int nranks, int rank, 
     s->d = cfg->topology == ACS_TOPO_CSR ? 0 : cfg->degree;
     s->dp = (cfg->degree + 3u) & ~3u;
     s->weighted = weighted;
+    s->pushsum = pushsum;
     s->nnz = csr_nnz;
     // "clean": no slot-dependent decision at all (no faults, no loss, no delays)
     s->clean = cfg->fault_model == ACS_FAULT_NONE && drop_threshold(cfg->loss_p) == 0 && cfg->delay_max == 0;
@@ -1161,7 +1220,8 @@ static int create_impl(const acs_config* cfg, int device, int nranks, int rank, 
         s->path = PATH_REGULAR;
         s->csr_var = true;
         s->dp = s->d;
-        s->kname = weighted ? std::string("k_round_weighted<") + std::to_string(s->d) + ",csr>"
+        s->kname = pushsum  ? std::string("k_round_pushsum<") + std::to_string(s->d) + ",csr>"
+                   : weighted ? std::string("k_round_weighted<") + std::to_string(s->d) + ",csr>"
                             : std::string("k_round_regular<") + std::to_string(s->d) + "," +
                                   std::to_string(cfg->trim) + ",csr>";
     } else if (s->m <= kGenericBigMaxM) {
@@ -1483,6 +1543,10 @@ static int create_impl(const acs_config* cfg, int device, int nranks, int rank, 
         CREATE_TRY(generic_big_build(s->big, ids, mv, s->f32, s->stream));
     }
     CREATE_TRY(launch_init_values(s->x[0], s->B, s->N, s->mp.key, cfg->instance_offset, s->f32, s->stream));
+    if (pushsum) {   // round 0: s = x^0, z = 1 (Npad == N: CSR handles are not partitioned)
+        CREATE_TRY(hipMalloc(&s->pairs, 2 * s->B * s->N * 2 * s->es));
+        CREATE_TRY(launch_pushsum_fill(s->x[0], pairs_at(s, 0), s->B * s->N, s->f32, s->stream));
+    }
     for (Part& q : s->parts)
         CREATE_TRY(launch_init_values(q.x[0], s->B, s->N, s->mp.key, cfg->instance_offset, s->f32, s->stream));
 #undef CREATE_TRY
@@ -1573,8 +1637,8 @@ int acs_create_csr(const acs_config* cfg, const uint64_t* rowptr, const uint32_t
     if (out) *out = nullptr;
     if (!cfg || cfg->topology != ACS_TOPO_CSR) return fail(ACS_EINVAL, "config topology must be ACS_TOPO_CSR");
     if (!rowptr || !colidx) return fail(ACS_EINVAL, "null CSR arrays");
-    if (cfg->rule == ACS_RULE_WEIGHTED)
-        return fail(ACS_EINVAL, "rule WEIGHTED needs weights: use acs_create_csr_weighted");
+    if (cfg->rule == ACS_RULE_WEIGHTED || cfg->rule == ACS_RULE_PUSHSUM)
+        return fail(ACS_EINVAL, "rules WEIGHTED and PUSHSUM need weights: use acs_create_csr_weighted");
     return create_impl(cfg, device, 1, 0, nullptr, 0, out, rowptr, colidx);
 }
 
@@ -1582,8 +1646,9 @@ int acs_create_csr_weighted(const acs_config* cfg, const uint64_t* rowptr, const
                             const double* w_self, const double* w_edge, int device, acs_sim** out) {
     if (out) *out = nullptr;
     if (!cfg || cfg->topology != ACS_TOPO_CSR) return fail(ACS_EINVAL, "config topology must be ACS_TOPO_CSR");
-    if (cfg->rule != ACS_RULE_WEIGHTED)
-        return fail(ACS_EINVAL, "acs_create_csr_weighted takes rule ACS_RULE_WEIGHTED only (got rule %u)", cfg->rule);
+    if (cfg->rule != ACS_RULE_WEIGHTED && cfg->rule != ACS_RULE_PUSHSUM)
+        return fail(ACS_EINVAL, "acs_create_csr_weighted takes rules ACS_RULE_WEIGHTED and ACS_RULE_PUSHSUM only (got rule %u)",
+                    cfg->rule);
     if (!rowptr || !colidx) return fail(ACS_EINVAL, "null CSR arrays");
     if (!w_self || !w_edge) return fail(ACS_EINVAL, "null weight arrays");
     return create_impl(cfg, device, 1, 0, nullptr, 0, out, rowptr, colidx, w_self, w_edge);
@@ -1591,7 +1656,7 @@ int acs_create_csr_weighted(const acs_config* cfg, const uint64_t* rowptr, const
 
 int acs_get_weights(acs_sim* s, double* w_self_out, uint64_t n, double* w_edge_out, uint64_t nnz) {
     if (!s || !w_self_out || (!w_edge_out && nnz)) return fail(ACS_EINVAL, "null argument");
-    if (!s->weighted) return fail(ACS_EINVAL, "acs_get_weights: not a rule-WEIGHTED handle");
+    if (!s->weighted) return fail(ACS_EINVAL, "acs_get_weights: not a handle of acs_create_csr_weighted");
     if (n != s->N || nnz != s->nnz)
         return fail(ACS_EINVAL, "acs_get_weights: expected n = %llu, nnz = %llu", (unsigned long long)s->N,
                     (unsigned long long)s->nnz);
@@ -1805,6 +1870,8 @@ int acs_set_state(acs_sim* s, uint32_t round, const void* x, uint64_t n) {
         float* cf = reinterpret_cast<float*>(canon.data());
         for (uint64_t k = 0; k < n; ++k) {
             if (!(fabsf(xf[k]) <= 1e30f)) return fail(ACS_EINVAL, "set_state: value %llu is not finite or |x| > 1e30", (unsigned long long)k);
+            if (s->pushsum && !(fabsf(xf[k]) <= kPushsumMaxAbs32))
+                return fail(ACS_EINVAL, "set_state: value %llu has |x| > 1e26 (PUSHSUM, fp32)", (unsigned long long)k);
             cf[k] = xf[k] + 0.0f;
         }
     } else {
@@ -1812,6 +1879,8 @@ int acs_set_state(acs_sim* s, uint32_t round, const void* x, uint64_t n) {
         double* cd = reinterpret_cast<double*>(canon.data());
         for (uint64_t k = 0; k < n; ++k) {
             if (!(fabs(xd[k]) <= 1e300)) return fail(ACS_EINVAL, "set_state: value %llu is not finite or |x| > 1e300", (unsigned long long)k);
+            if (s->pushsum && !(fabs(xd[k]) <= kPushsumMaxAbs64))
+                return fail(ACS_EINVAL, "set_state: value %llu has |x| > 1e290 (PUSHSUM)", (unsigned long long)k);
             cd[k] = xd[k] + 0.0;
         }
     }
@@ -1827,7 +1896,73 @@ int acs_set_state(acs_sim* s, uint32_t round, const void* x, uint64_t n) {
             HIP_TRY(hipMemcpyAsync(xat(s, q.x[round & 1u], b * s->Npad), hb, s->N * s->es, hipMemcpyHostToDevice,
                                    s->stream));
     }
+    if (s->pushsum)   // s = x, z = 1
+        HIP_TRY(launch_pushsum_fill(xb(s, round), pairs_at(s, round), s->B * s->N, s->f32, s->stream));
     return init_state(s, round);
+}
+
+int acs_get_pushsum_state(acs_sim* s, uint64_t b, void* s_out, void* z_out, uint64_t n) {
+    if (!s || !s_out || !z_out || b >= s->B || n < s->N) return fail(ACS_EINVAL, "bad get_pushsum_state arguments");
+    if (!s->pushsum) return fail(ACS_EINVAL, "acs_get_pushsum_state: not a rule-PUSHSUM handle");
+    HIP_TRY(hipSetDevice(s->device));
+    InstState e;
+    HIP_TRY(hipMemcpyAsync(&e, s->st + b, sizeof e, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    std::vector<unsigned char> h(s->N * 2 * s->es);
+    HIP_TRY(hipMemcpyAsync(h.data(), static_cast<char*>(pairs_at(s, e.rounds)) + b * s->N * 2 * s->es, h.size(),
+                           hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (s->f32) {
+        const float* p = reinterpret_cast<const float*>(h.data());
+        for (uint64_t k = 0; k < s->N; ++k) {
+            static_cast<float*>(s_out)[k] = p[2 * k];
+            static_cast<float*>(z_out)[k] = p[2 * k + 1];
+        }
+    } else {
+        const double* p = reinterpret_cast<const double*>(h.data());
+        for (uint64_t k = 0; k < s->N; ++k) {
+            static_cast<double*>(s_out)[k] = p[2 * k];
+            static_cast<double*>(z_out)[k] = p[2 * k + 1];
+        }
+    }
+    return ACS_OK;
+}
+
+int acs_set_pushsum_state(acs_sim* s, uint32_t round, const void* sv, const void* zv, uint64_t n) {
+    if (!s || !sv || !zv) return fail(ACS_EINVAL, "null argument");
+    if (!s->pushsum) return fail(ACS_EINVAL, "acs_set_pushsum_state: not a rule-PUSHSUM handle");
+    if (n != s->B * s->N) return fail(ACS_EINVAL, "set_pushsum_state needs B*N values in s and in z");
+    if (round > s->c.max_rounds) return fail(ACS_EINVAL, "round > max_rounds");
+    // the mass bound of DESIGN.md §9 admits |s| <= 1e290 (fp32: 1e26); z finite, >= 0 (z <= the same
+    // bound); -0.0 is stored as +0.0
+    std::vector<unsigned char> h(n * 2 * s->es);
+    if (s->f32) {
+        float* p = reinterpret_cast<float*>(h.data());
+        for (uint64_t k = 0; k < n; ++k) {
+            const float a = static_cast<const float*>(sv)[k], z = static_cast<const float*>(zv)[k];
+            if (!(fabsf(a) <= kPushsumMaxAbs32))
+                return fail(ACS_EINVAL, "set_pushsum_state: s[%llu] is not finite or |s| > 1e26", (unsigned long long)k);
+            if (!(z >= 0.0f && z <= kPushsumMaxAbs32))
+                return fail(ACS_EINVAL, "set_pushsum_state: z[%llu] must be finite, in [0, 1e26]", (unsigned long long)k);
+            p[2 * k] = a + 0.0f;
+            p[2 * k + 1] = z + 0.0f;
+        }
+    } else {
+        double* p = reinterpret_cast<double*>(h.data());
+        for (uint64_t k = 0; k < n; ++k) {
+            const double a = static_cast<const double*>(sv)[k], z = static_cast<const double*>(zv)[k];
+            if (!(fabs(a) <= kPushsumMaxAbs64))
+                return fail(ACS_EINVAL, "set_pushsum_state: s[%llu] is not finite or |s| > 1e290", (unsigned long long)k);
+            if (!(z >= 0.0 && z <= kPushsumMaxAbs64))
+                return fail(ACS_EINVAL, "set_pushsum_state: z[%llu] must be finite, in [0, 1e290]", (unsigned long long)k);
+            p[2 * k] = a + 0.0;
+            p[2 * k + 1] = z + 0.0;
+        }
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipMemcpyAsync(pairs_at(s, round), h.data(), h.size(), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(launch_pushsum_estimate(pairs_at(s, round), xb(s, round), n, s->f32, s->stream));
+    return init_state(s, round);   // (synchronises: h outlives the copy)
 }
 
 int acs_get_fault_status(acs_sim* s, uint32_t* out, uint64_t n) {

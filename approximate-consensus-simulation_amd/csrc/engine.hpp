@@ -9,6 +9,8 @@
 //               64 loads are one contiguous 1 KiB line run
 //   wself, wedge, well : rule WEIGHTED only: per-entry weights of the config dtype,
 //               [N], [nnz] by slot, and the edge weights again in the ELL's own order
+//   pairs     : rule PUSHSUM only: two buffers [B][N] of (s, z) pairs of the config
+//               dtype (double2 / float2); instance b at round r lives in pairs[r & 1], beside x
 //   status    : u32 [B][N] fault status (§A.4), absent when there are no faults
 //   st        : InstState [B] — honest lo/hi/spread of the current round, rounds, done flags
 //   partial   : double2 [B][nblk] per-block honest (min, max) partials of x^{r+1} (§A.8)
@@ -89,6 +91,10 @@ struct RoundArgs {
     const void* wself;
     const void* wedge;
     const void* well;
+    // rule PUSHSUM: the (s, z) pairs of round r and r + 1, instance-major [B][N] of
+    // double2 (fp32: float2); xin / xout hold the estimates s / z beside them
+    const void* pin;
+    void* pout;
 };
 constexpr uint32_t kEaccSlots = 32, kEaccStride = 16;       // eacc pairs, u64 words between pairs
 constexpr uint32_t kEaccWords = kEaccSlots * kEaccStride;   // eacc words of one round parity
@@ -191,6 +197,15 @@ hipError_t launch_round_weighted(const RoundArgs& a, uint64_t B, uint32_t nblk_f
 // wedge (CSR slot order) -> well (the ELL's order) for the rows deg[] does not mark as hubs
 hipError_t launch_weights_to_ell(const uint64_t* rowptr, const void* wedge, const uint8_t* deg, uint64_t N,
                                  uint32_t d, bool f32, void* well, hipStream_t s);
+
+// Rule PUSHSUM on a CSR graph (round_pushsum.hip): one lane per receiver over the same padded ELL
+// and weight array, a pair gather per sender; hub rows are skipped (k_round_generic's rule-6 branch).
+bool pushsum_fast_supported(uint32_t d);
+hipError_t launch_round_pushsum(const RoundArgs& a, uint64_t B, uint32_t nblk_fast, hipStream_t s);
+// pairs[k] = (x[k], 1) for n values (create, acs_set_state)
+hipError_t launch_pushsum_fill(const void* x, void* pairs, uint64_t n, bool f32, hipStream_t s);
+// x[k] = s / z where z > 0, else s (acs_set_pushsum_state)
+hipError_t launch_pushsum_estimate(const void* pairs, void* x, uint64_t n, bool f32, hipStream_t s);
 
 // Binned exchange (round_binned.hip): the one-instance RANDOM_REGULAR round as streaming kernels
 // instead of N·d random 8-byte gathers (clean, lossy and faulty configs; no delays).  Deliveries (i <- j) are grouped into

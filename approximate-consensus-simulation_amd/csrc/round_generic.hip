@@ -7,6 +7,7 @@
 // Used for the dense cfg2 shape (N = 1024 complete, t = 341) and any odd (d, t).
 #include <cstdlib>
 #include <mutex>
+#include <type_traits>
 
 #include "resolve.hpp"
 #include "sortnet.hpp"
@@ -200,6 +201,43 @@ __global__ __launch_bounds__(BLK) void k_round_generic(const RoundArgs a, uint32
             const VT res = den > VT(0) ? num / den : xi;
             xo[i] = res;
             *part = honest ? make_double2((double)res, (double)res) : make_double2(kInf, -kInf);
+        }
+        return;
+    }
+    if (a.rule == 6) {
+        // PUSHSUM (CSR rows, no faults, no delays): ps_e = (w_e * s_e) + 0.0 in one LDS
+        // half and pz_e = (w_e * z_e) + 0.0 in the other, one entry-order tree sum each, no
+        // normalisation; a dropped message (and the padding past m) adds +0.0 to both.  z' = 0 keeps x_i.
+        using V2 = typename std::conditional<sizeof(VT) == 4, float2, double2>::type;
+        const VT* __restrict__ ws = reinterpret_cast<const VT*>(a.wself);
+        const VT* __restrict__ we = reinterpret_cast<const VT*>(a.wedge);
+        const V2* __restrict__ pin = reinterpret_cast<const V2*>(a.pin) + lb * N;
+        for (uint32_t e = threadIdx.x; e < P; e += BLK) {
+            VT pe = VT(0), ze = VT(0);
+            if (e < m) {
+                const uint64_t slot = rp + e - 1;   // (entry 0 has no slot)
+                const bool dropped = e != 0 && mp.thr && draw(mp.key, kStreamDrop, bG, a.r, slot) < mp.thr;
+                if (!dropped) {
+                    const VT wt = e == 0 ? ws[i] : we[slot];
+                    const V2 v = pin[e == 0 ? i : a.colidx[slot]];
+                    pe = wt * v.x + VT(0);
+                    ze = wt * v.y + VT(0);
+                }
+            }
+            sh[e] = pe;
+            sh[P + e] = ze;
+        }
+        __syncthreads();
+        const VT num = block_tree_sum<BLK>(sh, P);
+        const VT den = block_tree_sum<BLK>(sh + P, P);
+        if (threadIdx.x == 0) {
+            const VT res = den > VT(0) ? num / den : xi;
+            V2 o;
+            o.x = num;
+            o.y = den;
+            (reinterpret_cast<V2*>(a.pout) + lb * N)[i] = o;
+            xo[i] = res;
+            *part = make_double2((double)res, (double)res);
         }
         return;
     }

@@ -27,7 +27,9 @@ extern "C" {
 
 #define ACS_ABI_VERSION 4   /* 2: acs_config.delay_max (bounded-delay rounds);
                                3: acs_config.missing_policy (was reserved0), acs_get_all_values;
-                               4: ACS_RULE_WEIGHTED, acs_create_csr_weighted, acs_get_weights */
+                               4: ACS_RULE_WEIGHTED, acs_create_csr_weighted, acs_get_weights
+                                  (still 4: ACS_RULE_PUSHSUM and acs_get / acs_set_pushsum_state are
+                                  additions; acs_config and every older symbol are unchanged) */
 
 /* status codes */
 #define ACS_OK            0
@@ -60,6 +62,15 @@ extern "C" {
  * weight (w_self[i], then w_edge[slot]); x_i' = tree_sum(w_e * v_e) / tree_sum(w_e).  CSR topology
  * and trim == 0 only; handles come from acs_create_csr_weighted */
 #define ACS_RULE_WEIGHTED      5
+/* Push-sum / ratio consensus on a directed CSR graph (Kempe, Dobra, Gehrke 2003):
+ * node i holds a pair (s_i, z_i), s_i = x_i^0 and z_i = 1 at round 0; a round sets
+ * s_i' = tree_sum(w_e * s_e), z_i' = tree_sum(w_e * z_e) over the receiver's entries with the
+ * weights of rule WEIGHTED (no normalisation) and x_i' = s_i' / z_i' (x_i is kept while z_i' = 0).
+ * With column sums of the weights equal to 1 the mass sum(s) / sum(z) is the mean of x^0, which
+ * every x_i approaches.  CSR topology, trim == 0, no faults, no delays; loss needs
+ * missing_policy = OMIT (a dropped message loses its mass).  Handles come from
+ * acs_create_csr_weighted */
+#define ACS_RULE_PUSHSUM       6
 
 /* fault model (§A.4) */
 #define ACS_FAULT_NONE       0
@@ -165,16 +176,23 @@ int acs_create_csr(const acs_config* cfg, const uint64_t* rowptr, const uint32_t
 
 /* DESIGN.md §9 (rule "weighted"): acs_create_csr with one weight per entry, shared by all
  * instances: w_self[N] for entry 0 and w_edge[rowptr[N]] indexed by slot.  cfg->rule must be
- * ACS_RULE_WEIGHTED (and only this entry point takes that rule) with cfg->trim == 0.  Every weight
+ * ACS_RULE_WEIGHTED or ACS_RULE_PUSHSUM (and only this entry point takes those rules) with
+ * cfg->trim == 0.  Every weight
  * must be finite with 0 <= w <= 1 and every row's weight sum positive; with cfg->dtype = ACS_F32
  * the weights are rounded to binary32 once, here, and checked after rounding.  All of this is
  * checked on the host before any device call (ACS_EINVAL).  Rows above 8192 entries are not
- * served yet (ACS_EUNSUPPORTED). */
+ * served yet (ACS_EUNSUPPORTED).
+ * ACS_RULE_PUSHSUM adds: every column sum (w_self[j] plus every w_edge[slot] with colidx[slot] == j,
+ * a compensated double sum of the weights as held) must be at most 1 + 2^-30, so the total mass
+ * cannot grow without bound; fault_model must be NONE and loss_p > 0 needs missing_policy = OMIT
+ * (ACS_EINVAL); delay_max > 0 is not served (ACS_EUNSUPPORTED); with ACS_F32, max_rounds <= 2^22
+ * (ACS_EINVAL; the bound that keeps every binary32 sum finite). */
 int acs_create_csr_weighted(const acs_config* cfg, const uint64_t* rowptr, const uint32_t* colidx,
                             const double* w_self, const double* w_edge, int device, struct acs_sim** out);
 
 /* The weights the device holds (fp32 handles: the rounded weights, widened back to double):
- * n = N values into w_self_out, nnz = rowptr[N] values into w_edge_out.  Weighted handles only. */
+ * n = N values into w_self_out, nnz = rowptr[N] values into w_edge_out.  Handles of
+ * acs_create_csr_weighted only (rules WEIGHTED and PUSHSUM). */
 int acs_get_weights(struct acs_sim* sim, double* w_self_out, uint64_t n, double* w_edge_out, uint64_t nnz);
 
 /* §8(e) node partitioning of ONE RANDOM_REGULAR instance over n_ranks GPUs (cfg5), one process
@@ -221,6 +239,17 @@ int acs_get_spread_trace(struct acs_sim* sim, uint64_t instance, double* out, ui
 /* Resume (§A.9): set every instance to round `round` with values x (B*N values, instance-major).
  * Instances become unfinished unless the EPS test already holds at `round`. */
 int acs_set_state(struct acs_sim* sim, uint32_t round, const void* x, uint64_t n);
+
+/* Rule PUSHSUM, ACS_EINVAL on any other handle.
+ * acs_get_pushsum_state: the pairs of one instance, n >= N values of the config dtype into each of
+ * s_out and z_out, read from the buffer of the instance's own round (as acs_get_values reads x).
+ * acs_set_pushsum_state: resume with pairs, n = B*N values of the config dtype in each array,
+ * instance-major.  |s| <= 1e290 (ACS_F32: 1e26), z finite and >= 0; -0.0 is stored as +0.0.  x is
+ * recomputed on the device: s / z where z > 0, and s where z = 0.  Spread and done flags restart as
+ * for acs_set_state.  On a push-sum handle acs_set_state(round, x) sets s = x and z = 1, with the
+ * same bound on |x|. */
+int acs_get_pushsum_state(struct acs_sim* sim, uint64_t instance, void* s_out, void* z_out, uint64_t n);
+int acs_set_pushsum_state(struct acs_sim* sim, uint32_t round, const void* s, const void* z, uint64_t n);
 
 /* Device-side fault schedule (§A.4): per node u32 status, 0xFFFFFFFF honest, 0xFFFFFFFE
  * Byzantine, otherwise the crash round r_v.  out holds B*N words. */
