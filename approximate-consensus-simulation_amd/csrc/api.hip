@@ -304,7 +304,7 @@ BinnedOptions acs::binned_options_from_env(bool f32) {
     if ((v = getenv("ACSIM_BIN_MIMG")) && strtod(v, nullptr) > 0) o.mimg = strtod(v, nullptr);
     if ((v = getenv("ACSIM_BIN_AWG"))) o.awg = strtoull(v, nullptr, 10);
     o.nofix = getenv("ACSIM_BIN_NOFIX") != nullptr;
-    if ((v = getenv("ACSIM_BIN_NARROW"))) o.narrow = v[0] == '1';
+    if ((v = getenv("ACSIM_BIN_NARROW"))) o.narrow = v[0] != '0';   // (on by default)
     if ((v = getenv("ACSIM_BIN_TS"))) {
         o.ts = true;
         o.ts_file = v;
@@ -1386,9 +1386,9 @@ static int create_impl(const acs_config* cfg, int device, int nranks, int rank, 
             CREATE_TRY(hipMemcpy(s->clist, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         }
     }
-    // what a binned plan of nr local rows is built for.  Narrow stage (ACSIM_BIN_NARROW=1, opt-in;
-    // DESIGN.md §5.15): whole unpartitioned rounds with the deferred finalize, whose phase B publishes
-    // each round's (min, max) for the next phase A
+    // what a binned plan of nr local rows is built for.  Narrow stage (the default where a plan
+    // qualifies): whole unpartitioned rounds with the deferred finalize, whose
+    // phase B publishes each round's (min, max) for the next phase A
     auto bin_desc = [&](uint64_t nr) {
         return BinnedDesc{s->N, nr, s->d, s->dp, tagged, s->f32, s->csr_var, s->clean, s->status,
                           !partitioned && s->defer_fin && s->eacc != nullptr};

@@ -234,7 +234,7 @@ struct BinnedOptions {
     double mimg = 16384.0;     // ACSIM_BIN_MIMG: target deliveries per phase-M image
     uint64_t awg = 0;          // ACSIM_BIN_AWG: phase-A workgroups per launch (0: the plan's choice)
     bool nofix = false;        // ACSIM_BIN_NOFIX: tagged senders even where a fix-up list would serve
-    bool narrow = false;       // ACSIM_BIN_NARROW=1: narrow stage where the plan qualifies
+    bool narrow = true;        // ACSIM_BIN_NARROW=0 turns it off: narrow stage where the plan qualifies
     bool ts = false;           // ACSIM_BIN_TS=<file>: workgroup timestamps, dumped when the plan is freed
     std::string ts_file;
 };
@@ -269,9 +269,10 @@ struct BinnedPlan {
     // delivery from a sender that is not honest; nullptr: tagged senders (k_bin_tag) instead
     uint4* fix = nullptr;
     uint32_t nfix = 0;
-    // narrow stage (ACSIM_BIN_NARROW=1; clean one-level fp64 plans): a round whose
-    // values all lie strictly on one side of zero within 2^32 ulps of each other stages u32 offsets
-    // from their base instead of 8-byte values; runs are then padded to 4 entries
+    // narrow stage (the default, ACSIM_BIN_NARROW=0 turns it off; clean one-level fp64 plans,
+    // DESIGN.md §5.15): a round whose values all lie strictly on one side of zero within 2^32 ulps
+    // of each other stages u32 offsets from their base instead of 8-byte values; runs are then
+    // padded to 4 entries
     bool narrow = false;
     uint4* nhdr = nullptr;              // the round's {base, width} (phase A writes, phase B reads)
 };

@@ -1,5 +1,6 @@
-"""Narrow stage A/B: whole run() of cfg4-shaped workloads with the default plan and
-with ACSIM_BIN_NARROW=1, alternating fresh handles inside one process, plus the rounds each run
+"""Narrow stage A/B: whole run() of cfg4-shaped workloads with the 8-byte plan
+(ACSIM_BIN_NARROW=0, "default" in the records: the default until the narrow plan became it) and
+with the narrow plan, alternating fresh handles inside one process, plus the rounds each run
 took and a golden-free cross-check (the two plans' final values must be bit-identical).
 
 usage: python tools/narrow_probe.py [reps]
@@ -26,10 +27,7 @@ WORKLOADS = {
 
 
 def one(name, narrow):
-    if narrow:
-        os.environ["ACSIM_BIN_NARROW"] = "1"
-    else:
-        os.environ.pop("ACSIM_BIN_NARROW", None)
+    os.environ["ACSIM_BIN_NARROW"] = "1" if narrow else "0"
     cfg = acsim.preset("cfg4", **WORKLOADS[name])
     with acsim.Simulator(cfg, device=0) as s:
         s.sync()

@@ -10,6 +10,7 @@ import sys
 
 def phases(path):
     rows = list(csv.DictReader(open(path)))
+    rows.sort(key=lambda r: int(r["Start_Timestamp"]))   # (the trace's rows are not always in dispatch order)
     dur = lambda r: (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3  # noqa: E731
     a = [dur(r) for r in rows if "k_bin_scatter" in r["Kernel_Name"]]
     b = [dur(r) for r in rows if "k_bin_gather" in r["Kernel_Name"]]
