@@ -323,6 +323,10 @@ __device__ __forceinline__ void bin_stream_pk14_narrow(const double* lx, const u
 // is base + k with 0 <= k <= omax - omin (base: the smaller pattern, i.e. the min for positive
 // values and the max for negative ones); with that span below 2^32, a u32 offset carries each
 // value exactly.  w = 8: full width (nothing published, a zero or mixed signs, or a wider span).
+// w = 0 (uniform round): omin == omax, every x^r is the one bit pattern `base` (ord is injective,
+// so equal ords are equal bits; any sign, zero included: no offset arithmetic is involved), and
+// every delivery of the round is known without a stage: phase A streams nothing and phase B
+// evaluates the rule on D + 1 copies of base.
 __device__ __forceinline__ void narrow_choose(unsigned long long omin, unsigned long long omax, uint32_t& w,
                                               unsigned long long& base) {
     constexpr unsigned long long kOrdPos0 = 1ull << 63;      // ord(+0.0)
@@ -330,6 +334,11 @@ __device__ __forceinline__ void narrow_choose(unsigned long long omin, unsigned 
     w = 8;
     base = 0;
     if (omin > omax) return;   // nothing published (the pair's identity decodes to NaNs)
+    if (omin == omax) {
+        w = 0;
+        base = (unsigned long long)__double_as_longlong(ord_inv(omin));
+        return;
+    }
     const bool pos = omin > kOrdPos0, neg = omax < kOrdNeg0;
     if (!(pos || neg) || omax - omin > 0xFFFFFFFFull) return;
     w = 4;

@@ -166,6 +166,11 @@ __global__ __launch_bounds__(kBinA) void k_bin_scatter(const VT* __restrict__ x,
     } else {
         __syncthreads();
     }
+    // Uniform round (narrow plans, width 0: every x^r is one bit pattern): phase B
+    // needs no stage, so nothing is streamed.  Workgroup 0 has recorded the header and the finalize
+    // above.  Like the `done || idle` exit this one lies behind a barrier whose vmcnt(0) has landed
+    // the x-block copies: no LDS-DMA write is in flight into LDS the CU's next workgroup will own.
+    if (nhdr && nar_w == 0u) return;
     const uint64_t t1 = ts ? __builtin_amdgcn_s_memrealtime() : 0;
     const uint32_t smode = (pol & kPolSc1Store) ? 2u : (pol & kPolNtStore) ? 1u : 0u;
     if (pkA) {   // 14-bit packed indices
@@ -363,8 +368,10 @@ __global__ __launch_bounds__(SB, FAULTY && NP > 1 ? ACS_FAULTY_WPE_OF(T, WMSR) :
     // narrow plans: this round's stage entry width (4: u32 offsets from the base in .x/.y), read
     // after the first loads this workgroup needs anyway, so that one wait covers both (read first,
     // it was waited for alone ahead of them: phase B +4-5 us in 8-byte rounds)
+    // Width 0 is a uniform round: every x^r is the bit pattern in .x/.y, so the D + 1 inputs of every
+    // receiver are known from the header alone (no stage, no LDS image, no invpos).
     uint4 nh = make_uint4(0u, 0u, 8u, 0u);
-    bool nar = false;
+    bool nar = false, uni = false;
     // NP-pass blocks of at most 64 runs: every wave fetches all descriptors first (one per lane)
     // and issues part 0's DMA before anything else is in flight, so the only wait ahead of the
     // first transfer is the descriptor load itself; later parts issue from registers.
@@ -391,11 +398,12 @@ __global__ __launch_bounds__(SB, FAULTY && NP > 1 ? ACS_FAULTY_WPE_OF(T, WMSR) :
             asm volatile("" ::: "memory");   // (issued after the descriptor loads)
             nh = bin_nhdr_load(a.nhdr);
             nar = nh.z == 4u;
+            uni = nh.z == 0u;
         }
         const uint32_t j1 = nrun / NP;
         hi0 = __builtin_amdgcn_readlane(pdsc.y, j1);
         if (adma) ppk = pdsc.y | ((pnxt - pdsc.y) / (16 / sizeof(VT))) << 16;
-        if (!nar) {   // (a narrow round copies its whole u32 image below)
+        if (!nar && !uni) {   // (a narrow round copies its whole u32 image below, a uniform one nothing)
             if (adma)
                 bin_dma_runs_asm(pdsc.x, ppk, w * j1 / NW, (w + 1) * j1 / NW, stage, raw, hi0 - cap);
             else
@@ -403,9 +411,11 @@ __global__ __launch_bounds__(SB, FAULTY && NP > 1 ? ACS_FAULTY_WPE_OF(T, WMSR) :
         }
     }
     if constexpr (NP > 1) {
-        if (clampm && !nar && threadIdx.x < 16 / sizeof(VT)) raw[cap + threadIdx.x] = VT(0);   // +0 bits
+        if (clampm && !nar && !uni && threadIdx.x < 16 / sizeof(VT)) raw[cap + threadIdx.x] = VT(0);   // +0 bits
     }
     // ordinary loads next (their wait is the barrier's vmcnt(0) anyway)
+    // (x_i is loaded in uniform rounds too, where it is the header's value: skipping the load in the
+    // prefetched kernels measured 2-3 us slower there and about 1.5 us in the 4-byte rounds)
     const VT xi = live ? reinterpret_cast<const VT*>(a.xin)[i] : VT(0);
     uint32_t si = kHonest;
     if constexpr (FLT) {
@@ -469,7 +479,9 @@ __global__ __launch_bounds__(SB, FAULTY && NP > 1 ? ACS_FAULTY_WPE_OF(T, WMSR) :
         }
     } else
 #endif
-    {   // once-read stream: nontemporal loads (phase B 80 -> 71 us on cfg4)
+    // (skipped in a uniform round the kernel already knows of: the prefetched kernels, which read the
+    // header first; the one-pass kernels learn the width after these loads)
+    if (!uni) {   // once-read stream: nontemporal loads (phase B 80 -> 71 us on cfg4)
         using u32x4 = unsigned int __attribute__((ext_vector_type(4)));
         const u32x4* ipn = reinterpret_cast<const u32x4*>(ipp);
 #pragma unroll
@@ -483,12 +495,19 @@ __global__ __launch_bounds__(SB, FAULTY && NP > 1 ? ACS_FAULTY_WPE_OF(T, WMSR) :
             asm volatile("" ::: "memory");
             nh = bin_nhdr_load(a.nhdr);
             nar = nh.z == 4u;
+            uni = nh.z == 0u;
         }
     }
     VT v[D + 1];
     bool picked = false;
     if constexpr (NAR) {
-        if (nar) {   // narrow round: the block's u32 image in one pass, values = base + offset
+        if (uni) {   // uniform round: every delivered value is the header's bit pattern (and so is x_i)
+            const VT u = __longlong_as_double((long long)((uint64_t)nh.x | (uint64_t)nh.y << 32));
+#pragma unroll
+            for (int t = 0; t < D; ++t) v[1 + t] = u;
+            if (a.ts) t1 = __builtin_amdgcn_s_memrealtime();
+            picked = true;
+        } else if (nar) {   // narrow round: the block's u32 image in one pass, values = base + offset
             uint32_t* r32 = reinterpret_cast<uint32_t*>(raw);
             const uint32_t* s32 = reinterpret_cast<const uint32_t*>(stage);
             if (pf) {

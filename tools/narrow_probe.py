@@ -3,10 +3,15 @@
 with the narrow plan, alternating fresh handles inside one process, plus the rounds each run
 took and a golden-free cross-check (the two plans' final values must be bit-identical).
 
-usage: python tools/narrow_probe.py [reps]
+usage: python tools/narrow_probe.py [reps [plan [workload...]]]
 One JSON line per run: workload, plan, rounds, wall µs per round of the whole run() (state on the
 device), kernel name.  Workloads: cfg4 FIXED 100 rounds (the bench workload), the driver's shape
-(FIXED 25 rounds: its timed rounds 5-25 sit inside), and cfg4 to ε = 1e-12 (EPS).
+(FIXED 25 rounds: its timed rounds 5-25 sit inside), cfg4 to ε = 1e-12 (EPS) and cfg4's natural run
+to ε = 1e-6 (14 rounds).
+
+plan = "narrow" or "default" runs that plan alone (no cross-check): for an A/B of two builds of the
+library, one process per build (ACSIM_LIB) and per rep, alternating; ACSIM_PROBE_TAG names the
+build in the records.
 """
 import json
 import os
@@ -23,6 +28,7 @@ WORKLOADS = {
     "cfg4_fixed100": dict(max_rounds=100, termination="fixed"),
     "cfg4_fixed25": dict(max_rounds=25, termination="fixed"),
     "cfg4_eps1e-12": dict(max_rounds=200, termination="eps", eps=1e-12),
+    "cfg4_eps1e-6": dict(max_rounds=200, termination="eps", eps=1e-6),
 }
 
 
@@ -44,7 +50,17 @@ def one(name, narrow):
 
 def main():
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 3
-    for name in WORKLOADS:
+    plan = sys.argv[2] if len(sys.argv) > 2 else "both"
+    names = sys.argv[3:] or list(WORKLOADS)
+    if plan != "both":
+        one(names[0], plan == "narrow")   # warm-up (code objects, allocations), not recorded
+        for name in names:
+            for rep in range(reps):
+                rec, _ = one(name, plan == "narrow")
+                rec.update(rep=rep, build=os.environ.get("ACSIM_PROBE_TAG", ""))
+                print(json.dumps(rec), flush=True)
+        return
+    for name in names:
         for rep in range(reps):
             xs = {}
             for narrow in ((False, True) if rep % 2 == 0 else (True, False)):

@@ -1,6 +1,6 @@
 """Per-round phase A / phase B device durations (µs) of default and narrow cfg4 runs from rocprofv3
-kernel traces (tools/sessions_scripts/r06_fin3.sh), with medians over the 8-byte rounds (1-14) and
-the 4-byte rounds (15 on) of the narrow plan.
+kernel traces (tools/sessions_scripts/r06_fin3.sh), with medians over the 8-byte rounds (1-14), the
+4-byte rounds (15-39) and the uniform rounds (40 on) of the narrow plan.
 usage: python tools/narrow_traces_json.py <session dir> <out.json> <tag>..."""
 import csv
 import json
@@ -27,10 +27,14 @@ def main():
         res["runs"][t] = {
             "phase_a_us": [round(x, 2) for x in a], "phase_b_us": [round(x, 2) for x in b],
             "median_rounds_1_14": {"a": st.median(a[101:115]), "b": st.median(b[101:115])},
-            "median_rounds_15_99": {"a": st.median(a[115:200]), "b": st.median(b[115:200])}}
+            "median_rounds_15_99": {"a": st.median(a[115:200]), "b": st.median(b[115:200])},
+            # cfg4's values are one bit pattern after round 39: rounds 40 on are uniform (width 0)
+            "median_rounds_15_39": {"a": st.median(a[115:139]), "b": st.median(b[115:139])},
+            "median_rounds_40_99": {"a": st.median(a[140:200]), "b": st.median(b[140:200])}}
     json.dump(res, open(out, "w"), indent=1)
     for t in tags:
-        print(t, res["runs"][t]["median_rounds_1_14"], res["runs"][t]["median_rounds_15_99"])
+        r = res["runs"][t]
+        print(t, r["median_rounds_1_14"], r["median_rounds_15_39"], r["median_rounds_40_99"])
 
 
 if __name__ == "__main__":
