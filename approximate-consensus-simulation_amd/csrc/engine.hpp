@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "binned_select.hpp"
+#include "csr_check.hpp"
 #include "spec.hpp"
 
 namespace acs {
@@ -311,8 +312,8 @@ hipError_t launch_round_binned(const BinnedPlan& p, const RoundArgs& a, bool cle
                                const FinalizeArgs* fin = nullptr, uint32_t phases = 7, SrcSel sel = SrcSel{});
 
 
-// Generic kernel: one workgroup per receiver, LDS bitonic sort (any topology, m <= 8192).
-constexpr uint32_t kGenericMaxM = 8192;   // receivers with more entries take the big-m path
+// Generic kernel: one workgroup per receiver, LDS bitonic sort (any topology, m <= kGenericMaxM =
+// 8192, csr_check.hpp; receivers with more entries take the big-m path).
 // nrecv: grid over a.rid's list (0: every receiver); Pcls: the list's size class (0: from a.m)
 hipError_t launch_round_generic(const RoundArgs& a, uint64_t B, hipStream_t s, uint64_t nrecv = 0, uint32_t Pcls = 0);
 // big-m path (round_generic.hip): receivers with kGenericMaxM < m_i <= kGenericBigMaxM, entries

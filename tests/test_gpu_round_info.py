@@ -1,7 +1,7 @@
 """round(k)'s info and the per-instance state getters against the oracle after every call.
 
 Handles of at most 16 instances read their states back through host-mapped memory (one small
-launch and a polled sequence number, `read_states` in api.hip); larger ones by a
+launch and a polled sequence number, `read_states` in rounds.hip); larger ones by a
 device-to-host copy.  Both paths, on the binned, per-lane, batched and persistent dense kernels,
 EPS and FIXED: round, done, instances done, spread / lo / hi, and the rounds / converged / spread
 getters, bit for bit after each call of a ragged step sequence.
