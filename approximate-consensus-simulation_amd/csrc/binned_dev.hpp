@@ -476,6 +476,25 @@ __device__ __forceinline__ void bin_dma_runs_asm_tb(const uint2* __restrict__ tb
 }
 __device__ __forceinline__ void bin_dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
+// phase B: x^{r+1}_i, plain or write-through (kPolSc1X: no dirty x lines left in L2 at the kernel boundary)
+template <int SB, typename VT>
+__device__ __forceinline__ void bin_store_x(const RoundArgs& a, uint64_t i, VT res, uint32_t pol) {
+    if (pol & kPolSc1X) {
+        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
+            reinterpret_cast<VT*>(a.xout) + (i - threadIdx.x), 0, (int)(SB * sizeof(VT)), 0x00020000);
+        if constexpr (sizeof(VT) == 8) {
+            using UV = unsigned int __attribute__((ext_vector_type(2)));
+            UV bits;
+            __builtin_memcpy(&bits, &res, 8);
+            __builtin_amdgcn_raw_buffer_store_b64(bits, rx, threadIdx.x * 8u, 0, 16);
+        } else {
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, res), rx, threadIdx.x * 4u, 0, 16);
+        }
+    } else {
+        reinterpret_cast<VT*>(a.xout)[i] = res;
+    }
+}
+
 // diagnostic (ACSIM_BIN_TS): workgroup entry, end of its staging wait, end, in 100 MHz ticks
 __device__ __forceinline__ void bin_ts(uint64_t* ts, uint64_t t0, uint64_t t1) {
     __syncthreads();

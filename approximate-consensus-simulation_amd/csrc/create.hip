@@ -126,6 +126,7 @@ BinnedOptions acs::binned_options_from_env(bool f32) {
     if ((v = getenv("ACSIM_BIN_AWG"))) o.awg = strtoull(v, nullptr, 10);
     o.nofix = getenv("ACSIM_BIN_NOFIX") != nullptr;
     if ((v = getenv("ACSIM_BIN_NARROW"))) o.narrow = v[0] != '0';   // (on by default)
+    if ((v = getenv("ACSIM_BIN_WEIGHTED"))) o.weighted = v[0] != '0';   // (off by default)
     if ((v = getenv("ACSIM_BIN_TS"))) {
         o.ts = true;
         o.ts_file = v;
@@ -230,7 +231,7 @@ void release(acs_sim* s) {
 // CSR on the register / binned paths (§8(f) row 1): the smallest compiled degree D >= the
 // largest row with the config's (t, rule), 0 if none (the generic kernel then runs).
 // (rules WEIGHTED and PUSHSUM have their own per-lane kernels, k_round_weighted<D> and
-// k_round_pushsum<D>, over the same padded rows)
+// k_round_pushsum<D>, over the same padded rows; WEIGHTED also a binned phase B, decide_binned)
 static bool csr_width_compiled(uint32_t d, uint32_t t, uint32_t rule) {
     if (rule == ACS_RULE_WEIGHTED) return t == 0 && weighted_fast_supported(d);
     if (rule == ACS_RULE_PUSHSUM) return t == 0 && pushsum_fast_supported(d);
@@ -342,13 +343,19 @@ static uint64_t decide_binned(acs_sim* s, const CreateOptions& o) {
     // there (at most 2^20 senders may crash in one round: n_faulty <= 2^20)
     const bool f32_tags_ok = !s->f32 || s->clean || s->N <= (1ull << 20) || c.fault_model != ACS_FAULT_CRASH ||
                              c.n_faulty <= (1u << 20);
+    // Rule WEIGHTED takes the exchange only where ACSIM_BIN_WEIGHTED asks for it: fp64
+    // CSR rows padded to a degree with a weighted phase B and no fault schedule (loss is served: phase
+    // B draws its own drop mask); every other weighted handle, and every PUSHSUM handle (16-byte
+    // pairs), keeps its per-lane kernel.
+    const bool rule_binned = s->weighted ? o.bin.weighted && c.rule == ACS_RULE_WEIGHTED && !s->f32 && s->csr_var &&
+                                               c.fault_model == ACS_FAULT_NONE && binned_weighted_supported(s->d)
+                                         : binned_supported(s->d, c.trim, c.rule);
     s->binned = o.bin.enabled && f32_tags_ok && s->path == PATH_REGULAR && c.delay_max == 0 &&
-                !(s->csr_var && s->f32) && !s->weighted &&   // (WEIGHTED: per-lane kernel only)
+                !(s->csr_var && s->f32) &&
                 // (CSR hub rows own the partial slots after the fast path's blocks; CSR plans
                 // always take kBinSB = kRegularBlock receivers per block, so both paths agree:
                 // static_assert in handle.hpp)
-                s->B == 1 && lv != 0 &&
-                binned_supported(s->d, c.trim, c.rule) && nrows * s->d < (1ull << 32);
+                s->B == 1 && lv != 0 && rule_binned && nrows * s->d < (1ull << 32);
     s->defer_fin = s->binned && !s->partitioned && s->B == 1 && o.defer_fin;
     // Block partials: one per receiver block of the round kernel.  The binned path's phase B writes
     // slot b of its bin_sb-row block b, the per-lane kernel slot b of its kRegularBlock-row block b;
@@ -632,8 +639,12 @@ static std::string kernel_name_of(const acs_sim* s) {
         // (levels and receiver block as decided for rows_per rows: a ragged or empty last rank's own
         // plan need not share them)
         const bool two = binned_levels(s->N, rows_local(s), s->d, s->bin_sa, s->bin_sb, nullptr) == 2;
-        nm = std::string("k_bin_scatter+") + (two ? "k_bin_regroup+" : "") + "k_bin_gather<" + std::to_string(s->d) + "," +
-             std::to_string(c.trim) + (s->clean ? "" : ",faulty") + (s->csr_var ? ",csr" : "") + ">";
+        nm = std::string("k_bin_scatter+") + (two ? "k_bin_regroup+" : "");
+        if (s->weighted)   // named after what runs: the lossy instantiation is no ",faulty" kernel
+            nm += "k_bin_gather_w<" + std::to_string(s->d) + ",csr>";
+        else
+            nm += "k_bin_gather<" + std::to_string(s->d) + "," + std::to_string(c.trim) + (s->clean ? "" : ",faulty") +
+                  (s->csr_var ? ",csr" : "") + ">";
         // fault fix-up list instead of tagged senders
         if (faults) nm += regular_plan && s->bin.fix ? "+k_bin_fixup" : "+k_bin_tag";
         if (s->bin_sb != kBinSB) nm += " sb" + std::to_string(s->bin_sb);

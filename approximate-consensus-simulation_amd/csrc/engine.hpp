@@ -236,6 +236,8 @@ struct BinnedOptions {
     uint64_t awg = 0;          // ACSIM_BIN_AWG: phase-A workgroups per launch (0: the plan's choice)
     bool nofix = false;        // ACSIM_BIN_NOFIX: tagged senders even where a fix-up list would serve
     bool narrow = true;        // ACSIM_BIN_NARROW=0 turns it off: narrow stage where the plan qualifies
+    bool weighted = false;     // ACSIM_BIN_WEIGHTED=1: rule WEIGHTED on the binned exchange where the handle
+                               // qualifies; off: every weighted handle on the per-lane kernel
     bool ts = false;           // ACSIM_BIN_TS=<file>: workgroup timestamps, dumped when the plan is freed
     std::string ts_file;
 };
@@ -278,6 +280,15 @@ struct BinnedPlan {
     uint4* nhdr = nullptr;              // the round's {base, width} (phase A writes, phase B reads)
 };
 bool binned_supported(uint32_t d, uint32_t t, uint32_t rule);
+// Rule WEIGHTED on a CSR plan (round_binned_w.hip): the padded degrees with a compiled
+// weighted phase B (fp64, one pass; invpos is read 8 slots at a time, so d = 4 stays per-lane)
+bool binned_weighted_supported(uint32_t d);
+// Phase B of such a plan over a.qlo .. a.qhi (Qc = blocks per XCD, as for k_bin_gather): the block's
+// runs of `stage` -> LDS, then num = sum w_e * v_e, den = sum w_e with the weights of a.wself / a.well;
+// the drop mask is drawn in the kernel when a.mp.thr != 0.  hipErrorNotSupported without a launch
+// for any other degree.
+hipError_t launch_bin_gather_w(const BinnedPlan& p, const RoundArgs& a, const double* stage, uint32_t Qc,
+                               hipStream_t s);
 // 1 or 2 exchange levels for NR local receivers of an N-node graph (0: not supported); sb = receiver block.
 uint32_t binned_levels(uint64_t N, uint64_t NR, uint32_t d, uint32_t sa, uint32_t sb, uint32_t* sr_out);
 // What a plan is built for: NR local rows of an N-node graph of degree d (ELL row width dp).

@@ -297,25 +297,6 @@ __global__ __launch_bounds__(256) void k_bin_fixup(const uint4* __restrict__ fix
 // delivery (k_bin_fixup), a missing one as a quiet NaN; phase B draws the §A.5 drop mask, turns
 // dropped and NaN entries into missing ones and applies the receiver's own status — no tag
 // decoding, no Byzantine draws, clean-kernel registers.
-// x^{r+1}_i, plain or write-through (kPolSc1X: no dirty x lines left in L2 at the kernel boundary)
-template <int SB, typename VT>
-__device__ __forceinline__ void bin_store_x(const RoundArgs& a, uint64_t i, VT res, uint32_t pol) {
-    if (pol & kPolSc1X) {
-        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-            reinterpret_cast<VT*>(a.xout) + (i - threadIdx.x), 0, (int)(SB * sizeof(VT)), 0x00020000);
-        if constexpr (sizeof(VT) == 8) {
-            using UV = unsigned int __attribute__((ext_vector_type(2)));
-            UV bits;
-            __builtin_memcpy(&bits, &res, 8);
-            __builtin_amdgcn_raw_buffer_store_b64(bits, rx, threadIdx.x * 8u, 0, 16);
-        } else {
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, res), rx, threadIdx.x * 4u, 0, 16);
-        }
-    } else {
-        reinterpret_cast<VT*>(a.xout)[i] = res;
-    }
-}
-
 // The narrow header as a scalar load (constant address space: phase A wrote it before this launch
 // and nothing writes it during one, so the scalar cache may serve it; as a vector load the compiler
 // made every workgroup wait for it alone before its first copies)
@@ -841,9 +822,10 @@ static constexpr auto kGatherLaunch = gather_launchers(std::make_index_sequence<
 
 // One round's launches for a plan of value type VT.  tag: the senders are tagged first (slot-dependent
 // rounds with a fault schedule and no fix-up); c: select_gather's choice of the phase-B kernel.
+// wgt: rule WEIGHTED (fp64 CSR plans; round_binned_w.hip): k_bin_gather_w in the place of c's row.
 template <typename VT>
 static hipError_t round_binned(const BinnedPlan& p, const RoundArgs& a, bool tag, const GatherChoice& c, hipStream_t s,
-                               const FinalizeArgs& fa, uint32_t fin_on, uint32_t phases, SrcSel sel) {
+                               const FinalizeArgs& fa, uint32_t fin_on, uint32_t phases, SrcSel sel, bool wgt = false) {
     constexpr bool kF32 = sizeof(VT) == 4;
     const uint32_t nsrc = sel.n ? sel.n : p.P;
     uint64_t* const ts_m = p.ts ? p.ts + 3ull * (p.ts_a + p.ts_b) : nullptr;
@@ -874,6 +856,9 @@ static hipError_t round_binned(const BinnedPlan& p, const RoundArgs& a, bool tag
     }
     if (c.fixp)
         hipLaunchKernelGGL(k_bin_fixup<VT>, dim3((p.nfix + 255) / 256), dim3(256), 0, s, p.fix, p.nfix, a, last, p.D);
+    if constexpr (!kF32) {
+        if (wgt) return (phases & 4) ? launch_bin_gather_w(p, a, last, (a.qhi - a.qlo + 7) / 8, s) : hipGetLastError();
+    }
     if (phases & 4) kGatherLaunch[c.row](p, a, last, (a.qhi - a.qlo + 7) / 8, s);
     return hipGetLastError();
 }
@@ -891,6 +876,18 @@ hipError_t launch_round_binned(const BinnedPlan& p, const RoundArgs& a0, bool cl
     const uint32_t nslot_all = a.nblk > p.Q ? a.nblk : p.Q;
     if (a.qhi > nslot_all) a.qhi = nslot_all;
     if (a.qlo >= a.qhi) phases &= ~4u;
+    const FinalizeArgs fa = fin ? *fin : FinalizeArgs{};
+    if (a.rule == 5) {
+        // Rule WEIGHTED: its phase B is no row of kGatherTable (GatherFacts::rule has no
+        // meaning for it).  Whole rounds of an untagged fp64 CSR plan only, refused before any launch;
+        // the phases then run exactly as for a clean or lossy VAR plan.
+        if (!p.var || p.f32 || a.status || sel.n || p.narrow || !binned_weighted_supported(p.D) || !a.well ||
+            !a.wself || !a.deg || (a.mp.thr && !a.rowptr))
+            return hipErrorInvalidValue;
+        a.nhdr = nullptr;
+        return round_binned<double>(p, a, false, GatherChoice{GatherErr::kNone, 0, false, false}, s, fa, fin ? 1u : 0u,
+                                    phases, sel, true);
+    }
     const GatherChoice c = select_gather({p.D, a.trim, a.rule, p.f32, clean, a.status != nullptr, p.var, p.split, p.SB,
                                           p.narrow, p.fix != nullptr, phases, sel.n, a.mp.omit != 0});
     if (c.err == GatherErr::kInvalidValue) return hipErrorInvalidValue;
@@ -898,7 +895,6 @@ hipError_t launch_round_binned(const BinnedPlan& p, const RoundArgs& a0, bool cl
     // a plan state without a compiled phase B: refused before anything is launched
     if ((phases & 4u) && c.err != GatherErr::kNone) return hipErrorNotSupported;
     const bool tag = !clean && a.status && !c.fixp;
-    const FinalizeArgs fa = fin ? *fin : FinalizeArgs{};
     return p.f32 ? round_binned<float>(p, a, tag, c, s, fa, fin ? 1u : 0u, phases, sel)
                  : round_binned<double>(p, a, tag, c, s, fa, fin ? 1u : 0u, phases, sel);
 }

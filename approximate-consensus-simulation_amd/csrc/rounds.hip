@@ -301,7 +301,8 @@ static int enqueue_round(acs_sim* s, uint32_t r) {
     // Invariant: EVERY kernel that writes a.partial in such a round must also publish into ab.eacc
     // (block_minmax_store(..., a.eacc)): k_bin_gather in all its forms (NP = 1 .. 4, VAR, FIX,
     // FAULTY, the narrow NAR kernels and the 128- / 512-receiver blocks: every row of kGatherTable,
-    // binned_select.hpp).  A writer that skipped it would not crash: phase A's other
+    // binned_select.hpp) and rule WEIGHTED's k_bin_gather_w (round_binned_w.hip).  A writer that
+    // skipped it would not crash: phase A's other
     // workgroups would stop on a stale verdict while workgroup 0 streams.  Hub rows (generic
     // kernel partials) and partitioned rounds are therefore excluded here;
     // tests/test_gpu_binned.py::test_eps_publication_in_every_gather_variant covers each form.
