@@ -9,6 +9,9 @@
   python -m acsim run --graph weighted.npz --set rule=weighted ...   (the file's weights too)
   python -m acsim run --graph directed.npz --set rule=pushsum ...   (the file's weights when it has
       them, else graphs.pushsum_weights; the choice is reported on stderr)
+  python -m acsim run --graph directed.npz --set rule=pushsum --set loss_p=0.2 --set missing_policy=hold
+      (push-sum under message loss: "hold" keeps a dropped message's mass on its link, so the mean of
+      x^0 is still found; "omit" loses the mass and ends away from it)
 """
 from __future__ import annotations
 

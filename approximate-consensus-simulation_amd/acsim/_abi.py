@@ -27,6 +27,7 @@ BYZ_SPLIT, BYZ_RANDOM, BYZ_CONSTANT = 0, 1, 2
 TERM_EPS, TERM_FIXED = 0, 1
 F64, F32 = 0, 1
 MISSING_SELF, MISSING_OMIT = 0, 1
+MISSING_HOLD = 2   # rule PUSHSUM only: a dropped message's mass waits on the link
 
 STREAM_INIT, STREAM_DROP, STREAM_FAULTSET, STREAM_CRASH_ROUND = 0, 1, 2, 3
 STREAM_CRASH_PARTIAL, STREAM_BYZ, STREAM_GRAPH = 4, 5, 6
@@ -129,6 +130,8 @@ def _declare(lib: C.CDLL) -> None:
         "acs_set_state": (i32, [vp, u32, vp, u64]),
         "acs_get_pushsum_state": (i32, [vp, u64, vp, vp, u64]),
         "acs_set_pushsum_state": (i32, [vp, u32, vp, vp, u64]),
+        "acs_get_pushsum_links": (i32, [vp, u64, vp, vp, u64]),
+        "acs_set_pushsum_links": (i32, [vp, vp, vp, u64]),
         "acs_get_fault_status": (i32, [vp, P(u32), u64]),
         "acs_get_neighbors": (i32, [vp, P(u32), u64]),
         "acs_set_kernel_timing": (i32, [vp, i32]),

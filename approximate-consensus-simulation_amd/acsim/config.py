@@ -24,7 +24,7 @@ _ENUMS = {
     "byz_strategy": {"split": _abi.BYZ_SPLIT, "random": _abi.BYZ_RANDOM,
                      "constant": _abi.BYZ_CONSTANT},
     "termination": {"eps": _abi.TERM_EPS, "fixed": _abi.TERM_FIXED},
-    "missing_policy": {"self": _abi.MISSING_SELF, "omit": _abi.MISSING_OMIT},
+    "missing_policy": {"self": _abi.MISSING_SELF, "omit": _abi.MISSING_OMIT, "hold": _abi.MISSING_HOLD},
     "dtype": {"f64": _abi.F64, "fp64": _abi.F64, "float64": _abi.F64, "f32": _abi.F32,
               "fp32": _abi.F32, "float32": _abi.F32},
 }
@@ -66,7 +66,8 @@ class Config:
     omp_threads: int = 0
     instance_offset: int = 0
     delay_max: int = 0          # bounded-delay rounds; 0 = synchronous
-    missing_policy: object = "self"   # "self" (§A.6 substitution) or "omit" 
+    missing_policy: object = "self"   # "self" (§A.6 substitution), "omit", or "hold" (rule "pushsum" only;
+                                      # DESIGN.md §9)
 
     def replace(self, **kw) -> "Config":
         return dataclasses.replace(self, **kw)

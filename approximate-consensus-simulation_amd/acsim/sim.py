@@ -8,6 +8,7 @@ oracle/, not part of the product).
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass
 from typing import Optional, Sequence
 
@@ -220,6 +221,44 @@ class Simulator:
             raise ValueError("s and z must have the same size")
         self._chk(self._lib.acs_set_pushsum_state(self._h, int(round), arrs[0].ctypes.data, arrs[1].ctypes.data,
                                                   arrs[0].size))
+
+    @property
+    def _hold(self) -> bool:
+        return int(self._c.rule) == _abi.RULE_PUSHSUM and int(self._c.missing_policy) == _abi.MISSING_HOLD
+
+    def pushsum_links(self, instance: int = 0):
+        """(h[nnz], k[nnz]) of one instance in slot order: the mass held on every link
+        (rule="pushsum" with missing_policy="hold")."""
+        nnz = getattr(self, "_nnz", 0)
+        h = np.empty(nnz, dtype=self.value_dtype)
+        k = np.empty(nnz, dtype=self.value_dtype)
+        self._chk(self._lib.acs_get_pushsum_links(self._h, int(instance), h.ctypes.data, k.ctypes.data, nnz))
+        return h, k
+
+    def set_pushsum_links(self, h: np.ndarray, k: np.ndarray) -> None:
+        """Set the held mass of every link, B*nnz values each (instance-major, slot order).
+        set_state and set_pushsum_state empty the links: a resume with held mass calls this after."""
+        arrs = []
+        for v in (h, k):
+            v = np.asarray(v)
+            if self.value_dtype == np.float32 and v.dtype != np.float32 and not np.array_equal(
+                    v.astype(np.float32).astype(v.dtype), v):
+                raise ValueError("fp32 set_pushsum_links: values must be exactly representable in binary32")
+            arrs.append(np.ascontiguousarray(v, dtype=self.value_dtype).reshape(-1))
+        if arrs[0].size != arrs[1].size:
+            raise ValueError("h and k must have the same size")
+        self._chk(self._lib.acs_set_pushsum_links(self._h, arrs[0].ctypes.data, arrs[1].ctypes.data, arrs[0].size))
+
+    def pushsum_mass(self, instance: int = 0):
+        """(fsum(s) + fsum(h), fsum(z) + fsum(k)) of one instance as Python floats: the mass on the
+        nodes plus the mass held on the links (missing_policy="hold"; without it the node sums
+        alone).  With column sums of 1 the second member stays N under "hold"."""
+        s, z = self.pushsum_state(instance)
+        ms, mz = math.fsum(s.tolist()), math.fsum(z.tolist())
+        if self._hold:
+            h, k = self.pushsum_links(instance)
+            ms, mz = ms + math.fsum(h.tolist()), mz + math.fsum(k.tolist())
+        return ms, mz
 
     def fault_status(self) -> np.ndarray:
         out = np.empty(self.B * self.N, dtype=np.uint32)

@@ -334,6 +334,8 @@ int acs_set_state(acs_sim* s, uint32_t round, const void* x, uint64_t n) {
     }
     if (s->pushsum)   // s = x, z = 1
         HIP_TRY(launch_pushsum_fill(xb(s, round), pairs_at(s, round), s->B * s->N, s->f32, s->stream));
+    if (s->hold)      // and every link empty (a resume with held mass calls acs_set_pushsum_links next)
+        HIP_TRY(hipMemsetAsync(s->links, 0, links_bytes(s), s->stream));
     return init_state(s, round);
 }
 
@@ -398,7 +400,74 @@ int acs_set_pushsum_state(acs_sim* s, uint32_t round, const void* sv, const void
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipMemcpyAsync(pairs_at(s, round), h.data(), h.size(), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(launch_pushsum_estimate(pairs_at(s, round), xb(s, round), n, s->f32, s->stream));
+    if (s->hold) HIP_TRY(hipMemsetAsync(s->links, 0, links_bytes(s), s->stream));   // as acs_set_state
     return init_state(s, round);   // (synchronises: h outlives the copy)
+}
+
+int acs_get_pushsum_links(acs_sim* s, uint64_t b, void* h_out, void* k_out, uint64_t n) {
+    if (!s) return fail(ACS_EINVAL, "null handle");
+    if (!s->hold) return fail(ACS_EINVAL, "acs_get_pushsum_links: not a rule-PUSHSUM handle with missing_policy = HOLD");
+    if (b >= s->B || n < s->nnz || ((!h_out || !k_out) && s->nnz))
+        return fail(ACS_EINVAL, "bad get_pushsum_links arguments (instance < B, n >= nnz = %llu)",
+                    (unsigned long long)s->nnz);
+    HIP_TRY(hipSetDevice(s->device));
+    std::vector<unsigned char> h(s->nnz * 2 * s->es);
+    if (s->nnz)
+        HIP_TRY(hipMemcpyAsync(h.data(), static_cast<char*>(s->links) + b * s->nnz * 2 * s->es, h.size(),
+                               hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (s->f32) {
+        const float* p = reinterpret_cast<const float*>(h.data());
+        for (uint64_t e = 0; e < s->nnz; ++e) {
+            static_cast<float*>(h_out)[e] = p[2 * e];
+            static_cast<float*>(k_out)[e] = p[2 * e + 1];
+        }
+    } else {
+        const double* p = reinterpret_cast<const double*>(h.data());
+        for (uint64_t e = 0; e < s->nnz; ++e) {
+            static_cast<double*>(h_out)[e] = p[2 * e];
+            static_cast<double*>(k_out)[e] = p[2 * e + 1];
+        }
+    }
+    return ACS_OK;
+}
+
+int acs_set_pushsum_links(acs_sim* s, const void* hv, const void* kv, uint64_t n) {
+    if (!s) return fail(ACS_EINVAL, "null handle");
+    if (!s->hold) return fail(ACS_EINVAL, "acs_set_pushsum_links: not a rule-PUSHSUM handle with missing_policy = HOLD");
+    if (n != s->B * s->nnz)
+        return fail(ACS_EINVAL, "set_pushsum_links needs B*nnz = %llu values in h and in k (got %llu)",
+                    (unsigned long long)(s->B * s->nnz), (unsigned long long)n);
+    if ((!hv || !kv) && n) return fail(ACS_EINVAL, "null argument");
+    // held mass takes the caps of s and z ("mass bound" under HOLD); -0.0 is stored as +0.0
+    std::vector<unsigned char> h(n * 2 * s->es);
+    if (s->f32) {
+        float* p = reinterpret_cast<float*>(h.data());
+        for (uint64_t e = 0; e < n; ++e) {
+            const float a = static_cast<const float*>(hv)[e], k = static_cast<const float*>(kv)[e];
+            if (!(fabsf(a) <= kPushsumMaxAbs32))
+                return fail(ACS_EINVAL, "set_pushsum_links: h[%llu] is not finite or |h| > 1e26", (unsigned long long)e);
+            if (!(k >= 0.0f && k <= kPushsumMaxAbs32))
+                return fail(ACS_EINVAL, "set_pushsum_links: k[%llu] must be finite, in [0, 1e26]", (unsigned long long)e);
+            p[2 * e] = a + 0.0f;
+            p[2 * e + 1] = k + 0.0f;
+        }
+    } else {
+        double* p = reinterpret_cast<double*>(h.data());
+        for (uint64_t e = 0; e < n; ++e) {
+            const double a = static_cast<const double*>(hv)[e], k = static_cast<const double*>(kv)[e];
+            if (!(fabs(a) <= kPushsumMaxAbs64))
+                return fail(ACS_EINVAL, "set_pushsum_links: h[%llu] is not finite or |h| > 1e290", (unsigned long long)e);
+            if (!(k >= 0.0 && k <= kPushsumMaxAbs64))
+                return fail(ACS_EINVAL, "set_pushsum_links: k[%llu] must be finite, in [0, 1e290]", (unsigned long long)e);
+            p[2 * e] = a + 0.0;
+            p[2 * e + 1] = k + 0.0;
+        }
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    if (n) HIP_TRY(hipMemcpyAsync(s->links, h.data(), h.size(), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));   // h outlives the copy
+    return ACS_OK;
 }
 
 int acs_get_fault_status(acs_sim* s, uint32_t* out, uint64_t n) {

@@ -83,14 +83,17 @@ int validate(const acs_config* c) {
         !(fabs(c->byz_delta) <= 1e30 && fabs(c->byz_const) <= 1e30))
         return fail(ACS_EINVAL, "fp32: byz_delta / byz_const must satisfy |.| <= 1e30");
     if (c->delay_max > 64) return fail(ACS_EINVAL, "delay_max must be <= 64");
-    if (c->missing_policy > ACS_MISSING_OMIT) return fail(ACS_EINVAL, "unknown missing_policy %u", c->missing_policy);
+    if (c->missing_policy > ACS_MISSING_HOLD) return fail(ACS_EINVAL, "unknown missing_policy %u", c->missing_policy);
+    if (c->missing_policy == ACS_MISSING_HOLD && c->rule != ACS_RULE_PUSHSUM)
+        return fail(ACS_EINVAL, "missing_policy = HOLD is defined for rule PUSHSUM only (got rule %u): held mass "
+                                "needs (s, z) pairs", c->rule);
     if (c->trace_spread && c->n_instances * ((uint64_t)c->max_rounds + 1) > (1ull << 28))
         return fail(ACS_EINVAL, "spread trace too large (B*(max_rounds+1) > 2^28)");
     if (c->rule == ACS_RULE_PUSHSUM) {
         if (c->fault_model != ACS_FAULT_NONE)
             return fail(ACS_EINVAL, "PUSHSUM is not defined under faults: Byzantine and crash values are "
                                     "defined on x, not on (s, z) pairs");
-        if (c->loss_p > 0.0 && c->missing_policy != ACS_MISSING_OMIT)
+        if (c->loss_p > 0.0 && c->missing_policy == ACS_MISSING_SELF)
             return fail(ACS_EINVAL, "PUSHSUM with loss_p > 0 needs missing_policy = OMIT: SELF would put the "
                                     "receiver's own pair in place of a lost message and create mass");
         if (c->delay_max > 0) return fail(ACS_EUNSUPPORTED, "PUSHSUM does not serve delay_max > 0 yet");
@@ -211,6 +214,7 @@ void release(acs_sim* s) {
     (void)hipFree(s->wedge);
     (void)hipFree(s->well);
     (void)hipFree(s->pairs);
+    (void)hipFree(s->links);
     (void)hipFree(s->gen_ids);
     (void)hipFree(s->crank);
     (void)hipFree(s->clist);
@@ -231,7 +235,8 @@ void release(acs_sim* s) {
 // CSR on the register / binned paths (§8(f) row 1): the smallest compiled degree D >= the
 // largest row with the config's (t, rule), 0 if none (the generic kernel then runs).
 // (rules WEIGHTED and PUSHSUM have their own per-lane kernels, k_round_weighted<D> and
-// k_round_pushsum<D>, over the same padded rows; WEIGHTED also a binned phase B, decide_binned)
+// k_round_pushsum<D> (under HOLD k_round_pushsum_hold<D>), over the same padded rows; WEIGHTED also
+// a binned phase B, decide_binned)
 static bool csr_width_compiled(uint32_t d, uint32_t t, uint32_t rule) {
     if (rule == ACS_RULE_WEIGHTED) return t == 0 && weighted_fast_supported(d);
     if (rule == ACS_RULE_PUSHSUM) return t == 0 && pushsum_fast_supported(d);
@@ -649,7 +654,8 @@ static std::string kernel_name_of(const acs_sim* s) {
         if (faults) nm += regular_plan && s->bin.fix ? "+k_bin_fixup" : "+k_bin_tag";
         if (s->bin_sb != kBinSB) nm += " sb" + std::to_string(s->bin_sb);
     } else if (s->csr_var) {
-        nm = s->pushsum  ? "k_round_pushsum<" + std::to_string(s->d) + ",csr>"
+        nm = s->hold     ? "k_round_pushsum_hold<" + std::to_string(s->d) + ",csr>"
+           : s->pushsum  ? "k_round_pushsum<" + std::to_string(s->d) + ",csr>"
            : s->weighted ? "k_round_weighted<" + std::to_string(s->d) + ",csr>"
                          : "k_round_regular<" + std::to_string(s->d) + "," + std::to_string(c.trim) + ",csr>";
     } else {
@@ -674,6 +680,10 @@ static int finish_handle(acs_sim* s, const CreateOptions& o, const void* comm_id
     if (s->pushsum) {   // round 0: s = x^0, z = 1 (Npad == N: CSR handles are not partitioned)
         STAGE_TRY(hipMalloc(&s->pairs, 2 * s->B * s->N * 2 * s->es));
         STAGE_TRY(launch_pushsum_fill(s->x[0], pairs_at(s, 0), s->B * s->N, s->f32, s->stream));
+    }
+    if (s->hold) {   // every link starts empty: (+0.0, +0.0)
+        STAGE_TRY(hipMalloc(&s->links, links_bytes(s)));
+        STAGE_TRY(hipMemsetAsync(s->links, 0, links_bytes(s), s->stream));
     }
     for (Part& q : s->parts)
         STAGE_TRY(launch_init_values(q.x[0], s->B, s->N, s->mp.key, c.instance_offset, s->f32, s->stream));
@@ -763,6 +773,7 @@ static acs_sim* new_handle(const acs_config& c, int device, int nranks, int rank
     s->generic_small = pc.generic_small;
     s->pushsum = c.rule == ACS_RULE_PUSHSUM;   // (weights as for WEIGHTED, one more rule)
     s->weighted = c.rule == ACS_RULE_WEIGHTED || s->pushsum;
+    s->hold = s->pushsum && c.missing_policy == ACS_MISSING_HOLD;   // (validate: HOLD only with PUSHSUM)
     s->nnz = chk.nnz;
     // "clean": no slot-dependent decision at all (no faults, no loss, no delays)
     s->clean = c.fault_model == ACS_FAULT_NONE && drop_threshold(c.loss_p) == 0 && c.delay_max == 0;

@@ -11,6 +11,8 @@
 //               [N], [nnz] by slot, and the edge weights again in the ELL's own order
 //   pairs     : rule PUSHSUM only: two buffers [B][N] of (s, z) pairs of the config
 //               dtype (double2 / float2); instance b at round r lives in pairs[r & 1], beside x
+//   links     : rule PUSHSUM with missing_policy = HOLD only: one buffer [B][nnz] of
+//               held (h, k) pairs in CSR slot order, updated in place by each slot's receiver
 //   status    : u32 [B][N] fault status (§A.4), absent when there are no faults
 //   st        : InstState [B] — honest lo/hi/spread of the current round, rounds, done flags
 //   partial   : double2 [B][nblk] per-block honest (min, max) partials of x^{r+1} (§A.8)
@@ -96,6 +98,11 @@ struct RoundArgs {
     // double2 (fp32: float2); xin / xout hold the estimates s / z beside them
     const void* pin;
     void* pout;
+    // rule PUSHSUM under missing_policy = HOLD: the held (h, k) pair of every CSR slot,
+    // [B][lnk_stride] of double2 (fp32: float2) in slot order, lnk_stride = nnz; read and written in
+    // place by the slot's receiver.  nullptr for every other handle.
+    void* lnk;
+    uint64_t lnk_stride;
 };
 constexpr uint32_t kEaccSlots = 32, kEaccStride = 16;       // eacc pairs, u64 words between pairs
 constexpr uint32_t kEaccWords = kEaccSlots * kEaccStride;   // eacc words of one round parity
@@ -203,6 +210,9 @@ hipError_t launch_weights_to_ell(const uint64_t* rowptr, const void* wedge, cons
 // and weight array, a pair gather per sender; hub rows are skipped (k_round_generic's rule-6 branch).
 bool pushsum_fast_supported(uint32_t d);
 hipError_t launch_round_pushsum(const RoundArgs& a, uint64_t B, uint32_t nblk_fast, hipStream_t s);
+// The same under missing_policy = HOLD (round_pushsum_hold.hip): a dropped message's mass stays on
+// its link (a.lnk, updated in place) and arrives with the next message that gets through.
+hipError_t launch_round_pushsum_hold(const RoundArgs& a, uint64_t B, uint32_t nblk_fast, hipStream_t s);
 // pairs[k] = (x[k], 1) for n values (create, acs_set_state)
 hipError_t launch_pushsum_fill(const void* x, void* pairs, uint64_t n, bool f32, hipStream_t s);
 // x[k] = s / z where z > 0, else s (acs_set_pushsum_state)

@@ -156,6 +156,11 @@ struct acs_sim {
     // two buffers [B][N]; instance b at round r lives in buffer r & 1
     bool pushsum = false;
     void* pairs = nullptr;
+    // ... under missing_policy = HOLD: the held (h, k) pair of every slot, one buffer [B][nnz] in CSR
+    // slot order (the public order, and the one k_round_generic indexes), zeroed at create; the round
+    // kernels update it in place.  Null for every other handle.
+    bool hold = false;
+    void* links = nullptr;
     double* dsorted = nullptr;     // dense path: sorted base multiset [N]
     uint32_t* dcounts = nullptr;   // dense path: |B|, #Byzantine, #crash-silent
     std::vector<Part> parts;       // virtual partitions 1..P-1 (partition 0 uses x / ell)
@@ -205,6 +210,8 @@ static inline void* xat(const acs_sim* s, const void* base, uint64_t k) {
 static inline void* pairs_at(const acs_sim* s, uint32_t q) {
     return static_cast<char*>(s->pairs) + (uint64_t)(q & 1u) * s->B * s->N * 2 * s->es;
 }
+// rule PUSHSUM under HOLD: bytes of the link buffer (at least one pair, so the pointer is never null)
+static inline uint64_t links_bytes(const acs_sim* s) { return (s->B * s->nnz ? s->B * s->nnz : 1) * 2 * s->es; }
 static inline uint64_t part_row0(const acs_sim* s, int p) { return (uint64_t)p * s->rows_per; }
 static inline uint64_t part_rows(const acs_sim* s, int p) {
     const uint64_t r0 = part_row0(s, p);

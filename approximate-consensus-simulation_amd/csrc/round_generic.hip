@@ -212,12 +212,28 @@ __global__ __launch_bounds__(BLK) void k_round_generic(const RoundArgs a, uint32
         const VT* __restrict__ ws = reinterpret_cast<const VT*>(a.wself);
         const VT* __restrict__ we = reinterpret_cast<const VT*>(a.wedge);
         const V2* __restrict__ pin = reinterpret_cast<const V2*>(a.pin) + lb * N;
+        // missing_policy = HOLD (a.lnk, round_pushsum_hold.hip): the slot's held pair takes the product
+        // (hn = h_e + a, kn = k_e + c); a delivered message contributes (hn, kn) and empties the link,
+        // a dropped one contributes +0.0 and leaves (hn, kn) on it.  In place: one thread per slot.
+        V2* lk = a.lnk ? reinterpret_cast<V2*>(a.lnk) + (uint64_t)lb * a.lnk_stride : nullptr;
         for (uint32_t e = threadIdx.x; e < P; e += BLK) {
             VT pe = VT(0), ze = VT(0);
             if (e < m) {
                 const uint64_t slot = rp + e - 1;   // (entry 0 has no slot)
                 const bool dropped = e != 0 && mp.thr && draw(mp.key, kStreamDrop, bG, a.r, slot) < mp.thr;
-                if (!dropped) {
+                if (lk && e != 0) {
+                    const VT wt = we[slot];
+                    const V2 v = pin[a.colidx[slot]];
+                    const V2 l = lk[slot];
+                    const VT hn = l.x + (wt * v.x + VT(0));
+                    const VT kn = l.y + (wt * v.y + VT(0));
+                    V2 keep;
+                    keep.x = dropped ? hn : VT(0);
+                    keep.y = dropped ? kn : VT(0);
+                    lk[slot] = keep;
+                    pe = dropped ? VT(0) : hn;
+                    ze = dropped ? VT(0) : kn;
+                } else if (!dropped) {
                     const VT wt = e == 0 ? ws[i] : we[slot];
                     const V2 v = pin[e == 0 ? i : a.colidx[slot]];
                     pe = wt * v.x + VT(0);

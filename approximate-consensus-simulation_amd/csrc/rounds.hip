@@ -156,6 +156,8 @@ static RoundArgs round_args(acs_sim* s, uint32_t r) {
     if (s->pushsum) {
         a.pin = pairs_at(s, r);
         a.pout = pairs_at(s, r + 1);
+        a.lnk = s->links;   // (HOLD handles only: null selects the plain rule in k_round_generic)
+        a.lnk_stride = s->nnz;
     }
     return a;
 }
@@ -320,6 +322,8 @@ static int enqueue_round(acs_sim* s, uint32_t r) {
             if (s->n_hub) ab.qhi = s->nblk_fast;   // the hub rows' partial slots are the generic kernel's
             HIP_TRY(launch_round_binned(s->bin, ab, s->clean, s->stream, s->fin_pending ? &s->fin_args : nullptr));
             s->fin_pending = false;
+        } else if (s->path == PATH_REGULAR && s->hold) {
+            HIP_TRY(launch_round_pushsum_hold(a, s->B, s->nblk_fast, s->stream));
         } else if (s->path == PATH_REGULAR && s->pushsum) {
             HIP_TRY(launch_round_pushsum(a, s->B, s->nblk_fast, s->stream));
         } else if (s->path == PATH_REGULAR && s->weighted) {

@@ -29,7 +29,8 @@ extern "C" {
                                3: acs_config.missing_policy (was reserved0), acs_get_all_values;
                                4: ACS_RULE_WEIGHTED, acs_create_csr_weighted, acs_get_weights
                                   (still 4: ACS_RULE_PUSHSUM and acs_get / acs_set_pushsum_state are
-                                  additions; acs_config and every older symbol are unchanged) */
+                                  additions; acs_config and every older symbol are unchanged;
+                                  likewise ACS_MISSING_HOLD and acs_get / acs_set_pushsum_links) */
 
 /* status codes */
 #define ACS_OK            0
@@ -68,8 +69,8 @@ extern "C" {
  * weights of rule WEIGHTED (no normalisation) and x_i' = s_i' / z_i' (x_i is kept while z_i' = 0).
  * With column sums of the weights equal to 1 the mass sum(s) / sum(z) is the mean of x^0, which
  * every x_i approaches.  CSR topology, trim == 0, no faults, no delays; loss needs
- * missing_policy = OMIT (a dropped message loses its mass).  Handles come from
- * acs_create_csr_weighted */
+ * missing_policy = OMIT (a dropped message loses its mass) or HOLD (it waits on the link, see
+ * ACS_MISSING_HOLD).  Handles come from acs_create_csr_weighted */
 #define ACS_RULE_PUSHSUM       6
 
 /* fault model (§A.4) */
@@ -91,6 +92,20 @@ extern "C" {
  * the trimming rules keep x_i when m_i <= 2t) */
 #define ACS_MISSING_SELF 0
 #define ACS_MISSING_OMIT 1
+/* HOLD (rule ACS_RULE_PUSHSUM only, ACS_EINVAL with any other rule): robust ratio
+ * consensus by running sums.  A dropped message's mass is not lost: it waits on the link and arrives
+ * with the next message that gets through.  Besides (s_i, z_i), every slot e = rowptr[i] + t of
+ * every instance holds a pair (h_e, k_e) of the config dtype, +0.0 at round 0.  Per sender entry e
+ * of receiver i, sender j = colidx[e]:
+ *   a = (w_e * s_j) + 0.0, c = (w_e * z_j) + 0.0    (as without HOLD: two roundings each, no FMA)
+ *   hn = h_e + a, kn = k_e + c                       (one rounding each)
+ *   dropped = loss_p > 0 && draw(key, DROP, bG, r, e) < thr     (the draw OMIT makes)
+ *   delivered: the entry contributes (hn, kn) to the two sums and the link stores (+0.0, +0.0)
+ *   dropped:   the entry contributes (+0.0, +0.0) and the link stores (hn, kn)
+ * Entry 0 (the receiver itself) has no link; sums, x and the stored pair are as without HOLD.  With
+ * column sums of 1, sum(z) + sum(k) stays N and every x_i approaches the mean of x^0 under loss,
+ * where OMIT ends away from it.  With loss_p = 0 a HOLD run equals the plain run bit for bit. */
+#define ACS_MISSING_HOLD 2
 
 /* value type (§A.0): fp64, or binary32 throughout */
 #define ACS_F64 0
@@ -185,7 +200,7 @@ int acs_create_csr(const acs_config* cfg, const uint64_t* rowptr, const uint32_t
  * ACS_RULE_PUSHSUM adds: every column sum (w_self[j] plus every w_edge[slot] with colidx[slot] == j,
  * a compensated double sum of the weights as held) must be at most 1 + 2^-30, so the total mass
  * cannot grow without bound; fault_model must be NONE and loss_p > 0 needs missing_policy = OMIT
- * (ACS_EINVAL); delay_max > 0 is not served (ACS_EUNSUPPORTED); with ACS_F32, max_rounds <= 2^22
+ * or HOLD (ACS_EINVAL); delay_max > 0 is not served (ACS_EUNSUPPORTED); with ACS_F32, max_rounds <= 2^22
  * (ACS_EINVAL; the bound that keeps every binary32 sum finite). */
 int acs_create_csr_weighted(const acs_config* cfg, const uint64_t* rowptr, const uint32_t* colidx,
                             const double* w_self, const double* w_edge, int device, struct acs_sim** out);
@@ -250,6 +265,17 @@ int acs_set_state(struct acs_sim* sim, uint32_t round, const void* x, uint64_t n
  * same bound on |x|. */
 int acs_get_pushsum_state(struct acs_sim* sim, uint64_t instance, void* s_out, void* z_out, uint64_t n);
 int acs_set_pushsum_state(struct acs_sim* sim, uint32_t round, const void* s, const void* z, uint64_t n);
+
+/* Rule PUSHSUM with missing_policy = ACS_MISSING_HOLD, ACS_EINVAL on any other handle: the held
+ * (h, k) pair of every link, in slot order (slot rowptr[i] + t carries colidx[slot] -> i).
+ * acs_get_pushsum_links: one instance's links, n >= nnz = rowptr[N] values of the config dtype
+ * into each of h_out and k_out.
+ * acs_set_pushsum_links: n = B*nnz values of the config dtype in each array, instance-major.
+ * |h| <= 1e290 (ACS_F32: 1e26), k finite, >= 0 and within the same cap; -0.0 is stored as +0.0.
+ * acs_set_state and acs_set_pushsum_state empty every link, so a resume with held mass calls
+ * acs_set_pushsum_links after them. */
+int acs_get_pushsum_links(struct acs_sim* sim, uint64_t instance, void* h_out, void* k_out, uint64_t n);
+int acs_set_pushsum_links(struct acs_sim* sim, const void* h, const void* k, uint64_t n);
 
 /* Device-side fault schedule (§A.4): per node u32 status, 0xFFFFFFFF honest, 0xFFFFFFFE
  * Byzantine, otherwise the crash round r_v.  out holds B*N words. */
