@@ -12,6 +12,9 @@
   python -m acsim run --graph directed.npz --set rule=pushsum --set loss_p=0.2 --set missing_policy=hold
       (push-sum under message loss: "hold" keeps a dropped message's mass on its link, so the mean of
       x^0 is still found; "omit" loses the mass and ends away from it)
+  python -m acsim run --graph scheduled.npz --set rule=pushsum --set missing_policy=hold
+      (a file with a link schedule, graphs.save_csr(..., schedule=...): rules weighted and pushsum run
+      on it, reported on stderr; push-sum keeps the mean on a schedule under "hold" only)
 """
 from __future__ import annotations
 
@@ -56,12 +59,21 @@ def _grid(specs):
     return grid
 
 
-def validate(cfg: Config, csr=None, weights=None) -> int:
+def validate(cfg: Config, csr=None, weights=None, schedule=None) -> int:
     """Host-side §A.8 validation through the library (no GPU needed: acs_create validates first)."""
     lib = _abi.load_library()
     c = cfg.to_c()
     h = C.c_void_p()
-    if csr is not None and weights is not None:
+    if csr is not None and weights is not None and schedule is not None:
+        rp, ci = csr
+        ws, we = (np.ascontiguousarray(w, dtype=np.float64) for w in weights)
+        av = np.ascontiguousarray(schedule[1], dtype=np.uint32)
+        dp = C.POINTER(C.c_double)
+        rc = lib.acs_create_csr_scheduled(C.byref(c), rp.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                          ci.ctypes.data_as(C.POINTER(C.c_uint32)), ws.ctypes.data_as(dp),
+                                          we.ctypes.data_as(dp), int(schedule[0]),
+                                          av.ctypes.data_as(C.POINTER(C.c_uint32)), 0, C.byref(h))
+    elif csr is not None and weights is not None:
         rp, ci = csr
         ws, we = (np.ascontiguousarray(w, dtype=np.float64) for w in weights)
         dp = C.POINTER(C.c_double)
@@ -104,7 +116,7 @@ def main(argv=None) -> int:
             print(k, json.dumps(dataclasses.asdict(v)))
         return 0
     cfg = _apply(preset(a.preset), a.set)
-    csr = weights = None
+    csr = weights = schedule = None
     if a.graph:
         from .config import _enum
         from .graphs import load_csr
@@ -126,23 +138,30 @@ def main(argv=None) -> int:
                       file=sys.stderr)
         else:
             csr = load_csr(a.graph)
+        if weights is not None:   # rules weighted and pushsum: the file's link schedule, when it has one
+            try:
+                schedule = load_csr(a.graph, schedule=True)[2:]
+                print(f"{cfg.rule}: using the link schedule of {a.graph} (period {schedule[0]})", file=sys.stderr)
+            except ValueError as e:
+                if "no link schedule" not in str(e):
+                    raise
         cfg = cfg.replace(topology="csr", n_nodes=int(csr[0].size - 1))
     if a.cmd == "validate":
-        rc = validate(cfg, csr, weights)
+        rc = validate(cfg, csr, weights, schedule)
         if rc == 0:
             print("ok")
         return rc
     if a.cmd == "run":
         from .io import save_result
         from .sim import simulate
-        res = simulate(cfg, device=a.device, return_values=bool(a.out), csr=csr, weights=weights)
+        res = simulate(cfg, device=a.device, return_values=bool(a.out), csr=csr, weights=weights, schedule=schedule)
         from .sweep import summarize
         print(json.dumps(summarize(cfg, res)))
         if a.out:
             save_result(a.out, res, cfg)
         return 0
     from .sweep import sweep
-    rows = sweep(cfg, _grid(a.grid), out_dir=a.out, device=a.device, csr=csr, weights=weights)
+    rows = sweep(cfg, _grid(a.grid), out_dir=a.out, device=a.device, csr=csr, weights=weights, schedule=schedule)
     for r in rows:
         print(json.dumps(r))
     return 0

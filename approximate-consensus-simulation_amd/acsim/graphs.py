@@ -39,26 +39,34 @@ def skewed_csr(n: int, dmin: int, dmax: int, seed: int, alpha: float = 2.0):
 # Weights (rule "weighted") are optional: acsim's layout adds w_self (float64 [N]) and
 # w_edge (float64 [nnz], by slot); in the scipy layout w_edge = data and w_self = 0 (a diagonal
 # entry is an ordinary self-loop message on its slot, with its own weight).
+# A link schedule is optional too, in acsim's layout only: sched_period (uint32 scalar)
+# and sched_avail (uint32 [nnz], by slot).
 # Receiver i's senders are colidx[rowptr[i] : rowptr[i+1]] in slot order (slot = rowptr[i] + t,
 # SURVEY §A.3).  Files are loaded with allow_pickle=False: a graph file executes nothing.
 
-def save_csr(path: str, rowptr, colidx, weights=None) -> None:
+def save_csr(path: str, rowptr, colidx, weights=None, schedule=None) -> None:
     """Write a CSR graph in acsim's `.npz` layout (validated first); weights = (w_self, w_edge)
-    are stored beside it for rule "weighted"."""
+    are stored beside it for rule "weighted", and schedule = (period, avail) as sched_period and
+    sched_avail (a link schedule, checked by check_schedule)."""
     rp, ci = check_csr(rowptr, colidx)
     extra = {}
     if weights is not None:
         ws, we = check_weights(rp, weights[0], weights[1])
         extra = {"w_self": ws, "w_edge": we}
+    if schedule is not None:
+        period, av = check_schedule(rp, schedule[0], schedule[1])
+        extra.update(sched_period=np.array(period, dtype=np.uint32), sched_avail=av)
     np.savez(path, rowptr=rp, colidx=ci, format=np.array("acsim-csr-v1"), **extra)
 
 
-def load_csr(path: str, weights: bool = False):
+def load_csr(path: str, weights: bool = False, schedule: bool = False):
     """Read a CSR graph file (acsim or scipy.sparse layout) -> (rowptr uint64[N+1], colidx uint32[nnz]).
     weights=True also returns the file's weights, (rowptr, colidx, w_self, w_edge): the arrays
     w_self / w_edge of acsim's layout, or w_edge = data and w_self = 0 for a scipy.sparse matrix;
-    a file without weights is a ValueError."""
-    ws = we = None
+    a file without weights is a ValueError.  schedule=True appends the file's link schedule
+    (period, avail) to the result; a file without one (sched_period / sched_avail of acsim's layout)
+    is a ValueError."""
+    ws = we = sched = None
     with np.load(path, allow_pickle=False) as z:
         keys = set(z.files)
         if {"rowptr", "colidx"} <= keys:
@@ -67,6 +75,8 @@ def load_csr(path: str, weights: bool = False):
                 if not {"w_self", "w_edge"} <= keys:
                     raise ValueError(f"{path}: no weights (w_self / w_edge) in {sorted(keys)}")
                 ws, we = z["w_self"], z["w_edge"]
+            if schedule and {"sched_period", "sched_avail"} <= keys:
+                sched = (int(z["sched_period"]), z["sched_avail"])
         elif {"indptr", "indices"} <= keys:
             if "format" in keys and str(z["format"].astype(str)) != "csr":
                 raise ValueError(f"{path}: scipy.sparse matrix in {z['format']!s} format; CSR expected")
@@ -83,9 +93,10 @@ def load_csr(path: str, weights: bool = False):
         else:
             raise ValueError(f"{path}: no CSR arrays (rowptr/colidx or indptr/indices) in {sorted(keys)}")
     rp, ci = check_csr(rp, ci)
-    if weights:
-        return (rp, ci) + check_weights(rp, ws, we)
-    return rp, ci
+    if schedule and sched is None:
+        raise ValueError(f"{path}: no link schedule (sched_period / sched_avail) in {sorted(keys)}")
+    out = (rp, ci) + (check_weights(rp, ws, we) if weights else ())
+    return out + check_schedule(rp, *sched) if schedule else out
 
 
 def check_weights(rowptr, w_self, w_edge):
@@ -100,6 +111,80 @@ def check_weights(rowptr, w_self, w_edge):
     if ws.shape != (rp.size - 1,) or we.shape != (int(rp[-1]),):
         raise ValueError("weights must be (w_self[N], w_edge[nnz])")
     return ws.astype(np.float64), we.astype(np.float64)
+
+
+# ---------------------------------------------------------------------------- link schedules
+# DESIGN.md §9, "Link schedules": a period P in 1..32 and one uint32 mask per CSR slot; bit p < P of
+# avail[slot] is set when the link on that slot is up in every round r with r % P == p.
+
+SCHEDULE_MAX_PERIOD = 32
+
+
+def check_schedule(rowptr, period, avail, values: bool = True):
+    """Shape and type of a link schedule for the graph `rowptr` -> (int period, uint32 [nnz]).
+    values=True also applies the value rules of acs_create_csr_scheduled: 1 <= period <= 32 and no
+    bit of any mask at a position >= period (the first offending slot is named)."""
+    rp = np.asarray(rowptr)
+    av = np.asarray(avail)
+    if isinstance(period, (bool, np.bool_)) or not isinstance(period, (int, np.integer)):
+        raise ValueError("schedule period must be an integer")
+    period = int(period)
+    if not np.issubdtype(av.dtype, np.integer) or av.dtype == np.bool_:
+        raise ValueError("schedule masks must be an integer array")
+    if av.shape != (int(rp[-1]),):
+        raise ValueError("schedule masks must be avail[nnz], one per CSR slot")
+    if not 0 <= period < 1 << 32 or (av.size and (int(av.min()) < 0 or int(av.max()) >= 1 << 32)):
+        raise ValueError("schedule period and masks must fit in uint32")
+    av = np.ascontiguousarray(av, dtype=np.uint32)
+    if values:
+        if not 1 <= period <= SCHEDULE_MAX_PERIOD:
+            raise ValueError(f"schedule period {period} outside 1..{SCHEDULE_MAX_PERIOD}")
+        stray = np.flatnonzero(av >> np.uint32(period)) if period < 32 else np.empty(0, dtype=np.int64)
+        if stray.size:
+            e = int(stray[0])
+            raise ValueError(f"avail[{e}] = {int(av[e]):#010x} has a bit at a position >= period {period}")
+    return period, av
+
+
+def full_schedule(nnz: int, period: int):
+    """The schedule on which every link is up in every phase: (period, avail[nnz]) with every mask
+    (1 << period) - 1.  A handle made with it equals the unscheduled handle bit for bit."""
+    if not 1 <= int(period) <= SCHEDULE_MAX_PERIOD:
+        raise ValueError(f"schedule period {period} outside 1..{SCHEDULE_MAX_PERIOD}")
+    return int(period), np.full(int(nnz), (1 << int(period)) - 1, dtype=np.uint32)
+
+
+def _mix64(v):
+    """The finaliser of splitmix64 on a uint64 array (arithmetic modulo 2^64)."""
+    v = np.asarray(v, dtype=np.uint64).copy()
+    v ^= v >> np.uint64(30)
+    v *= np.uint64(0xBF58476D1CE4E5B9)
+    v ^= v >> np.uint64(27)
+    v *= np.uint64(0x94D049BB133111EB)
+    v ^= v >> np.uint64(31)
+    return v
+
+
+def phase_schedule(rowptr, colidx, period: int, seed: int = 0, symmetric: bool = False):
+    """Exactly one phase per slot (TDMA-style link activation): slot e is up in the rounds r with
+    r % period == phase(e) and down in all others, so its longest down streak is period - 1 rounds.
+    With mix = the splitmix64 finaliser and all arithmetic modulo 2^64,
+        phase(e) = mix(mix(seed + 0x9E3779B97F4A7C15) + e) % period,
+    and with symmetric=True, for slot e of receiver i with sender j = colidx[e],
+        phase(e) = mix(mix(mix(seed + 0x9E3779B97F4A7C15) + min(i, j)) + max(i, j)) % period,
+    so both directions of an edge (and parallel edges) share a phase.  Returns (period, avail[nnz])."""
+    rp, ci = check_csr(rowptr, colidx)
+    if not 1 <= int(period) <= SCHEDULE_MAX_PERIOD:
+        raise ValueError(f"schedule period {period} outside 1..{SCHEDULE_MAX_PERIOD}")
+    period = int(period)
+    s0 = _mix64(np.array([(int(seed) + 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF], dtype=np.uint64))
+    if symmetric:
+        rows = np.repeat(np.arange(rp.size - 1, dtype=np.uint64), np.diff(rp.astype(np.int64)))
+        cols = ci.astype(np.uint64)
+        h = _mix64(_mix64(s0 + np.minimum(rows, cols)) + np.maximum(rows, cols))
+    else:
+        h = _mix64(s0 + np.arange(ci.size, dtype=np.uint64))
+    return period, (np.uint32(1) << (h % np.uint64(period)).astype(np.uint32)).astype(np.uint32)
 
 
 def metropolis_weights(rowptr, colidx):

@@ -45,7 +45,7 @@ class Simulator:
 
     def __init__(self, cfg: Config | str, device: int = 0, backend: str = "hip",
                  partitions: int = 1, rank: int = 0, comm_id: Optional[bytes] = None,
-                 csr=None, weights=None):
+                 csr=None, weights=None, schedule=None):
         """partitions > 1 node-partitions one RANDOM_REGULAR instance: with
         comm_id (RCCL unique id from acsim.distributed) this handle is `rank`'s partition on
         `device`; without it all partitions are simulated on `device` with private x copies
@@ -53,7 +53,12 @@ class Simulator:
 
         weights = (w_self[N], w_edge[nnz]) with csr and rule="weighted" or rule="pushsum"
         (DESIGN.md §9): receiver i's own entry weighs w_self[i], the message on slot s weighs
-        w_edge[s].  For "pushsum" the column sums must not exceed 1 (graphs.pushsum_weights)."""
+        w_edge[s].  For "pushsum" the column sums must not exceed 1 (graphs.pushsum_weights).
+
+        schedule = (period, avail[nnz]) with csr and weights ("Link schedules"): bit p of
+        avail[s] is set when the link on slot s is up in every round r with r % period == p; a message on
+        a slot that is down is missing exactly as a dropped one.  Push-sum keeps the mean on a schedule
+        only with missing_policy="hold" ("omit" loses the mass of every down link)."""
         if isinstance(cfg, str):
             cfg = preset(cfg)
         if backend != "hip":
@@ -66,6 +71,8 @@ class Simulator:
         h = C.c_void_p()
         if weights is not None and csr is None:
             raise ValueError("weights need a csr graph")
+        if schedule is not None and (csr is None or weights is None):
+            raise ValueError("a link schedule needs a csr graph with weights (rule 'weighted' or 'pushsum')")
         if csr is not None and weights is not None:   # rule="weighted" / "pushsum" (acs_create_csr_weighted)
             rp = np.ascontiguousarray(csr[0], dtype=np.uint64)
             ci = np.ascontiguousarray(csr[1], dtype=np.uint32)
@@ -77,9 +84,17 @@ class Simulator:
                 raise ValueError("weights must be (w_self[n_nodes], w_edge[len(colidx)])")
             self._nnz = int(ci.size)
             dp = C.POINTER(C.c_double)
-            rc = self._lib.acs_create_csr_weighted(
-                C.byref(self._c), rp.ctypes.data_as(C.POINTER(C.c_uint64)), ci.ctypes.data_as(C.POINTER(C.c_uint32)),
-                ws.ctypes.data_as(dp), we.ctypes.data_as(dp), int(device), C.byref(h))
+            if schedule is not None:   # acs_create_csr_scheduled checks the period and the masks' bits
+                from .graphs import check_schedule
+                period, av = check_schedule(rp, schedule[0], schedule[1], values=False)
+                rc = self._lib.acs_create_csr_scheduled(
+                    C.byref(self._c), rp.ctypes.data_as(C.POINTER(C.c_uint64)), ci.ctypes.data_as(C.POINTER(C.c_uint32)),
+                    ws.ctypes.data_as(dp), we.ctypes.data_as(dp), period, av.ctypes.data_as(C.POINTER(C.c_uint32)),
+                    int(device), C.byref(h))
+            else:
+                rc = self._lib.acs_create_csr_weighted(
+                    C.byref(self._c), rp.ctypes.data_as(C.POINTER(C.c_uint64)), ci.ctypes.data_as(C.POINTER(C.c_uint32)),
+                    ws.ctypes.data_as(dp), we.ctypes.data_as(dp), int(device), C.byref(h))
         elif csr is not None:   # user graph (topology="csr"): csr = (rowptr[N+1], colidx[nnz])
             rp = np.ascontiguousarray(csr[0], dtype=np.uint64)
             ci = np.ascontiguousarray(csr[1], dtype=np.uint32)
@@ -275,6 +290,14 @@ class Simulator:
         self._chk(self._lib.acs_get_weights(self._h, ws.ctypes.data_as(dp), ws.size, we.ctypes.data_as(dp), we.size))
         return ws, we
 
+    def link_schedule(self):
+        """(period, avail[nnz] uint32 in slot order) of a handle made with schedule=...."""
+        period = C.c_uint32()
+        av = np.empty(getattr(self, "_nnz", 0), dtype=np.uint32)
+        self._chk(self._lib.acs_get_link_schedule(self._h, C.byref(period), av.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                  av.size))
+        return int(period.value), av
+
     def neighbors(self) -> np.ndarray:
         d = int(self.cfg.degree)
         out = np.empty(self.N * d, dtype=np.uint32)
@@ -305,7 +328,7 @@ class Simulator:
 
 def simulate(cfg: Config | str, backend: str = "hip", device: int = 0,
              devices: Optional[Sequence[int]] = None, return_values: bool = True,
-             csr=None, weights=None) -> Result:
+             csr=None, weights=None, schedule=None) -> Result:
     """Run one configuration to termination and return its results."""
     if devices is not None:
         devices = list(devices)
@@ -313,7 +336,7 @@ def simulate(cfg: Config | str, backend: str = "hip", device: int = 0,
             raise ValueError("simulate() drives one device per process; shard instances across "
                              "processes with acsim.distributed (one rank per GPU)")
         device = devices[0]
-    with Simulator(cfg, device=device, backend=backend, csr=csr, weights=weights) as sim:
+    with Simulator(cfg, device=device, backend=backend, csr=csr, weights=weights, schedule=schedule) as sim:
         res = sim.run()
         x = None
         if return_values:

@@ -25,11 +25,11 @@ int fail(int code, const char* fmt, ...) {
 static int validate_and_create(const acs_config* cfg, int device, int nranks, int rank, const void* comm_id,
                                uint64_t id_len, acs_sim** out, const uint64_t* rowptr = nullptr,
                                const uint32_t* colidx = nullptr, const double* w_self = nullptr,
-                               const double* w_edge = nullptr) {
+                               const double* w_edge = nullptr, const LinkSchedule* sched = nullptr) {
     if (!out) return fail(ACS_EINVAL, "null out");
     *out = nullptr;
     if (int rc = validate(cfg)) return rc;
-    return create_impl(cfg, device, nranks, rank, comm_id, id_len, out, rowptr, colidx, w_self, w_edge);
+    return create_impl(cfg, device, nranks, rank, comm_id, id_len, out, rowptr, colidx, w_self, w_edge, sched);
 }
 
 // ------------------------------------------------------------------------- C ABI
@@ -88,6 +88,29 @@ int acs_create_csr_weighted(const acs_config* cfg, const uint64_t* rowptr, const
     if (!rowptr || !colidx) return fail(ACS_EINVAL, "null CSR arrays");
     if (!w_self || !w_edge) return fail(ACS_EINVAL, "null weight arrays");
     return validate_and_create(cfg, device, 1, 0, nullptr, 0, out, rowptr, colidx, w_self, w_edge);
+}
+
+int acs_create_csr_scheduled(const acs_config* cfg, const uint64_t* rowptr, const uint32_t* colidx, const double* w_self,
+                             const double* w_edge, uint32_t period, const uint32_t* avail, int device, acs_sim** out) {
+    if (out) *out = nullptr;
+    if (!cfg || cfg->topology != ACS_TOPO_CSR) return fail(ACS_EINVAL, "config topology must be ACS_TOPO_CSR");
+    if (cfg->rule != ACS_RULE_WEIGHTED && cfg->rule != ACS_RULE_PUSHSUM)
+        return fail(ACS_EUNSUPPORTED, "link schedules are served for rules WEIGHTED and PUSHSUM (got rule %u)", cfg->rule);
+    if (!rowptr || !colidx) return fail(ACS_EINVAL, "null CSR arrays");
+    if (!w_self || !w_edge) return fail(ACS_EINVAL, "null weight arrays");
+    const LinkSchedule sched{period, avail};   // (checked with the arrays: sched_check.hpp)
+    return validate_and_create(cfg, device, 1, 0, nullptr, 0, out, rowptr, colidx, w_self, w_edge, &sched);
+}
+
+int acs_get_link_schedule(acs_sim* s, uint32_t* period_out, uint32_t* avail_out, uint64_t nnz) {
+    if (!s || !period_out || (!avail_out && nnz)) return fail(ACS_EINVAL, "null argument");
+    if (!s->sched) return fail(ACS_EINVAL, "acs_get_link_schedule: not a handle of acs_create_csr_scheduled");
+    if (nnz != s->nnz) return fail(ACS_EINVAL, "acs_get_link_schedule: expected nnz = %llu", (unsigned long long)s->nnz);
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    *period_out = s->period;
+    if (nnz) HIP_TRY(hipMemcpy(avail_out, s->avail, nnz * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return ACS_OK;
 }
 
 int acs_get_weights(acs_sim* s, double* w_self_out, uint64_t n, double* w_edge_out, uint64_t nnz) {

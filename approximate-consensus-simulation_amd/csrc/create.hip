@@ -3,6 +3,7 @@
 // creation stages in order; each returns an ACS code (message through fail) and create_impl
 // releases the handle when one fails.  SURVEY §8(b), §8(e).
 #include "handle.hpp"
+#include "sched_check.hpp"
 
 using namespace acs;
 
@@ -215,6 +216,8 @@ void release(acs_sim* s) {
     (void)hipFree(s->well);
     (void)hipFree(s->pairs);
     (void)hipFree(s->links);
+    (void)hipFree(s->avail);
+    (void)hipFree(s->avell);
     (void)hipFree(s->gen_ids);
     (void)hipFree(s->crank);
     (void)hipFree(s->clist);
@@ -351,8 +354,9 @@ static uint64_t decide_binned(acs_sim* s, const CreateOptions& o) {
     // Rule WEIGHTED takes the exchange only where ACSIM_BIN_WEIGHTED asks for it: fp64
     // CSR rows padded to a degree with a weighted phase B and no fault schedule (loss is served: phase
     // B draws its own drop mask); every other weighted handle, and every PUSHSUM handle (16-byte
-    // pairs), keeps its per-lane kernel.
-    const bool rule_binned = s->weighted ? o.bin.weighted && c.rule == ACS_RULE_WEIGHTED && !s->f32 && s->csr_var &&
+    // pairs), keeps its per-lane kernel; so does every handle with a link schedule (phase B has no
+    // availability test).
+    const bool rule_binned = s->weighted ? o.bin.weighted && c.rule == ACS_RULE_WEIGHTED && !s->f32 && s->csr_var && !s->sched &&
                                                c.fault_model == ACS_FAULT_NONE && binned_weighted_supported(s->d)
                                          : binned_supported(s->d, c.trim, c.rule);
     s->binned = o.bin.enabled && f32_tags_ok && s->path == PATH_REGULAR && c.delay_max == 0 &&
@@ -534,7 +538,7 @@ static int build_regular(acs_sim* s, const CreateOptions& o) {
 // register / binned paths the padded ELL (SELL-64 slice widths), sorted rows when
 // order-independent, the weights in the ELL's order and the binned plan.
 static int build_csr(acs_sim* s, const CreateOptions& o, const CsrCheck& chk, const uint64_t* h_rowptr,
-                     const uint32_t* h_colidx) {
+                     const uint32_t* h_colidx, const LinkSchedule* h_sched) {
     const uint64_t nnz = s->nnz;
     STAGE_TRY(hipMalloc(&s->rowptr, (s->N + 1) * sizeof(uint64_t)));
     STAGE_TRY(hipMalloc(&s->colidx, (nnz ? nnz : 1) * sizeof(uint32_t)));
@@ -552,6 +556,10 @@ static int build_csr(acs_sim* s, const CreateOptions& o, const CsrCheck& chk, co
             if (nnz) STAGE_TRY(hipMemcpy(s->wedge, chk.wev.data(), nnz * sizeof(double), hipMemcpyHostToDevice));
         }
     }
+    if (s->sched) {   // the masks in slot order (k_round_generic, acs_get_link_schedule)
+        STAGE_TRY(hipMalloc(&s->avail, (nnz ? nnz : 1) * sizeof(uint32_t)));
+        if (nnz) STAGE_TRY(hipMemcpy(s->avail, h_sched->avail, nnz * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
     if (!s->csr_var) return ACS_OK;
     const uint64_t words = ((s->N + 63) / 64) * 64ull * s->dp;
     STAGE_TRY(hipMalloc(&s->ell, words * sizeof(uint32_t)));
@@ -563,6 +571,10 @@ static int build_csr(acs_sim* s, const CreateOptions& o, const CsrCheck& chk, co
     if (s->weighted) {
         STAGE_TRY(hipMalloc(&s->well, words * s->es));
         STAGE_TRY(launch_weights_to_ell(s->rowptr, s->wedge, s->deg, s->N, s->d, s->f32, s->well, s->stream));
+    }
+    if (s->sched) {   // ... and in the weights' order
+        STAGE_TRY(hipMalloc(&s->avell, words * sizeof(uint32_t)));
+        STAGE_TRY(launch_avail_to_ell(s->rowptr, s->avail, s->deg, s->N, s->d, s->avell, s->stream));
     }
     if (!s->binned) return ACS_OK;
     const hipError_t be = binned_build(s->bin, s->ell, bin_desc(s, s->N), o.bin, kBinSB, s->stream);
@@ -654,9 +666,10 @@ static std::string kernel_name_of(const acs_sim* s) {
         if (faults) nm += regular_plan && s->bin.fix ? "+k_bin_fixup" : "+k_bin_tag";
         if (s->bin_sb != kBinSB) nm += " sb" + std::to_string(s->bin_sb);
     } else if (s->csr_var) {
-        nm = s->hold     ? "k_round_pushsum_hold<" + std::to_string(s->d) + ",csr>"
-           : s->pushsum  ? "k_round_pushsum<" + std::to_string(s->d) + ",csr>"
-           : s->weighted ? "k_round_weighted<" + std::to_string(s->d) + ",csr>"
+        const std::string w = "<" + std::to_string(s->d) + (s->sched ? ",csr,sched>" : ",csr>");   // (SCHED instantiations)
+        nm = s->hold     ? "k_round_pushsum_hold" + w
+           : s->pushsum  ? "k_round_pushsum" + w
+           : s->weighted ? "k_round_weighted" + w
                          : "k_round_regular<" + std::to_string(s->d) + "," + std::to_string(c.trim) + ",csr>";
     } else {
         nm = regular_fast_name(s->d, c.trim, s->clean);
@@ -724,7 +737,7 @@ static int finish_handle(acs_sim* s, const CreateOptions& o, const void* comm_id
 // Checks that need no handle: the CSR arrays and weights, the partition arguments, the device.
 static int check_arguments(const acs_config* cfg, int device, int nranks, int rank, const void* comm_id,
                            uint64_t id_len, const uint64_t* h_rowptr, const uint32_t* h_colidx, const double* h_wself,
-                           const double* h_wedge, CsrCheck& chk) {
+                           const double* h_wedge, const LinkSchedule* h_sched, CsrCheck& chk) {
     if (cfg->topology == ACS_TOPO_CSR) {   // §8(f) row 1: check the arrays on the host
         if (!h_rowptr || !h_colidx) return fail(ACS_EINVAL, "CSR topology needs acs_create_csr(rowptr, colidx)");
         if (nranks != 1) return fail(ACS_EUNSUPPORTED, "node partitioning needs RANDOM_REGULAR");
@@ -735,6 +748,8 @@ static int check_arguments(const acs_config* cfg, int device, int nranks, int ra
         if (csr_check_weights(chk, *cfg, h_rowptr, h_colidx, h_wself, h_wedge))
             return fail(chk.code, "%s", chk.message.c_str());
     }
+    if (h_sched && sched_check(chk, *cfg, chk.nnz, h_sched->period, h_sched->avail))
+        return fail(chk.code, "%s", chk.message.c_str());
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail(ACS_EINVAL, "bad rank / n_ranks");
     const bool partitioned = nranks > 1 || comm_id != nullptr;
     if (partitioned && !comm_id && rank != 0) return fail(ACS_EINVAL, "virtual partitions live on one handle (rank 0)");
@@ -756,7 +771,7 @@ static int check_arguments(const acs_config* cfg, int device, int nranks, int ra
 
 // The handle's fields that follow from the config, the partition arguments and the path alone.
 static acs_sim* new_handle(const acs_config& c, int device, int nranks, int rank, bool partitioned, bool virt,
-                           const PathChoice& pc, const CsrCheck& chk) {
+                           const PathChoice& pc, const CsrCheck& chk, const LinkSchedule* h_sched) {
     acs_sim* s = new acs_sim();
     s->c = c;
     s->device = device;
@@ -775,8 +790,10 @@ static acs_sim* new_handle(const acs_config& c, int device, int nranks, int rank
     s->weighted = c.rule == ACS_RULE_WEIGHTED || s->pushsum;
     s->hold = s->pushsum && c.missing_policy == ACS_MISSING_HOLD;   // (validate: HOLD only with PUSHSUM)
     s->nnz = chk.nnz;
-    // "clean": no slot-dependent decision at all (no faults, no loss, no delays)
-    s->clean = c.fault_model == ACS_FAULT_NONE && drop_threshold(c.loss_p) == 0 && c.delay_max == 0;
+    s->sched = h_sched != nullptr;
+    s->period = h_sched ? h_sched->period : 0;
+    // "clean": no slot-dependent decision at all (no faults, no loss, no delays, no link schedule)
+    s->clean = c.fault_model == ACS_FAULT_NONE && drop_threshold(c.loss_p) == 0 && c.delay_max == 0 && !s->sched;
     s->mp.key = key_of(c.seed);
     s->mp.thr = drop_threshold(c.loss_p);
     s->mp.fault = c.fault_model;
@@ -801,11 +818,11 @@ static acs_sim* new_handle(const acs_config& c, int device, int nranks, int rank
 
 int create_impl(const acs_config* cfg, int device, int nranks, int rank, const void* comm_id, uint64_t id_len,
                 acs_sim** out, const uint64_t* h_rowptr, const uint32_t* h_colidx, const double* h_wself,
-                const double* h_wedge) {
+                const double* h_wedge, const LinkSchedule* h_sched) {
     *out = nullptr;
     // 1. host checks and 2. path choice, before any handle exists
     CsrCheck chk;
-    if (int rc = check_arguments(cfg, device, nranks, rank, comm_id, id_len, h_rowptr, h_colidx, h_wself, h_wedge, chk))
+    if (int rc = check_arguments(cfg, device, nranks, rank, comm_id, id_len, h_rowptr, h_colidx, h_wself, h_wedge, h_sched, chk))
         return rc;
     const CreateOptions opt = options_from_env(cfg->dtype == ACS_F32);
     const bool partitioned = nranks > 1 || comm_id != nullptr;
@@ -813,7 +830,7 @@ int create_impl(const acs_config* cfg, int device, int nranks, int rank, const v
     if (int rc = choose_path(*cfg, opt, partitioned, chk.mmax, h_rowptr, pc)) return rc;
 
     RoctxRange range("acs: create (graph, plan, fault schedule, x0)");
-    acs_sim* s = new_handle(*cfg, device, nranks, rank, partitioned, partitioned && !comm_id, pc, chk);
+    acs_sim* s = new_handle(*cfg, device, nranks, rank, partitioned, partitioned && !comm_id, pc, chk, h_sched);
     // 3. - 7.: the order matters in three places.  eacc (alloc_state) exists before any
     // binned_build, whose bin_desc reads it; the fault status is built before the plans, whose fix-up
     // list reads it; and `binned` is decided (decide_binned) before the fp32 crash-rank table.
@@ -821,7 +838,7 @@ int create_impl(const acs_config* cfg, int device, int nranks, int rank, const v
     int rc = alloc_state(s, opt, ncap);
     if (!rc) rc = build_fault_schedule(s);
     if (!rc && cfg->topology == ACS_TOPO_RANDOM_REGULAR) rc = build_regular(s, opt);
-    if (!rc && cfg->topology == ACS_TOPO_CSR) rc = build_csr(s, opt, chk, h_rowptr, h_colidx);
+    if (!rc && cfg->topology == ACS_TOPO_CSR) rc = build_csr(s, opt, chk, h_rowptr, h_colidx, h_sched);
     if (!rc) rc = build_generic_lists(s, h_rowptr);
     if (!rc) rc = finish_handle(s, opt, comm_id);
     if (rc) {

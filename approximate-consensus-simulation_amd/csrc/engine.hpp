@@ -103,6 +103,14 @@ struct RoundArgs {
     // place by the slot's receiver.  nullptr for every other handle.
     void* lnk;
     uint64_t lnk_stride;
+    // link schedule ("Link schedules"; rules WEIGHTED and PUSHSUM on CSR graphs): one
+    // availability mask per CSR slot, shared by all instances, in slot order (avail: the generic
+    // kernel) and in well's slice / group / lane order with 0 in absent columns (avell: the SCHED
+    // per-lane kernels).  phase = 1u << (r mod period): the slot is down in round r, its message
+    // missing exactly as a dropped one, when its mask lacks that bit.  nullptr, 0: no schedule.
+    const uint32_t* avail;
+    const uint32_t* avell;
+    uint32_t phase;
 };
 constexpr uint32_t kEaccSlots = 32, kEaccStride = 16;       // eacc pairs, u64 words between pairs
 constexpr uint32_t kEaccWords = kEaccSlots * kEaccStride;   // eacc words of one round parity
@@ -205,6 +213,9 @@ hipError_t launch_round_weighted(const RoundArgs& a, uint64_t B, uint32_t nblk_f
 // wedge (CSR slot order) -> well (the ELL's order) for the rows deg[] does not mark as hubs
 hipError_t launch_weights_to_ell(const uint64_t* rowptr, const void* wedge, const uint8_t* deg, uint64_t N,
                                  uint32_t d, bool f32, void* well, hipStream_t s);
+// a link schedule's masks, slot order -> the same order (0 in absent columns and hub rows)
+hipError_t launch_avail_to_ell(const uint64_t* rowptr, const uint32_t* avail, const uint8_t* deg, uint64_t N,
+                               uint32_t d, uint32_t* avell, hipStream_t s);
 
 // Rule PUSHSUM on a CSR graph (round_pushsum.hip): one lane per receiver over the same padded ELL
 // and weight array, a pair gather per sender; hub rows are skipped (k_round_generic's rule-6 branch).

@@ -161,6 +161,13 @@ struct acs_sim {
     // kernels update it in place.  Null for every other handle.
     bool hold = false;
     void* links = nullptr;
+    // link schedule ("Link schedules"; handles of acs_create_csr_scheduled): the slots'
+    // availability masks, shared by all instances, held twice: in slot order (the public view, and
+    // the one k_round_generic indexes) and, on the per-lane path, in well's order (0 in absent columns)
+    bool sched = false;
+    uint32_t period = 0;
+    uint32_t* avail = nullptr;     // [nnz]
+    uint32_t* avell = nullptr;     // (csr_var; RoundArgs::avell)
     double* dsorted = nullptr;     // dense path: sorted base multiset [N]
     uint32_t* dcounts = nullptr;   // dense path: |B|, #Byzantine, #crash-silent
     std::vector<Part> parts;       // virtual partitions 1..P-1 (partition 0 uses x / ell)
@@ -220,11 +227,16 @@ static inline uint64_t part_rows(const acs_sim* s, int p) {
 }
 
 // ---- create.hip
+struct LinkSchedule {   // acs_create_csr_scheduled's arguments as given (sched_check.hpp checks them)
+    uint32_t period;
+    const uint32_t* avail;
+};
 int validate(const acs_config* c);   // §A.8 constraints
 // A handle for a validated config (the callers in api.hip validate); *out is null on any failure.
 int create_impl(const acs_config* cfg, int device, int nranks, int rank, const void* comm_id, uint64_t id_len,
                 acs_sim** out, const uint64_t* h_rowptr = nullptr, const uint32_t* h_colidx = nullptr,
-                const double* h_wself = nullptr, const double* h_wedge = nullptr);
+                const double* h_wself = nullptr, const double* h_wedge = nullptr,
+                const LinkSchedule* h_sched = nullptr);
 void release(acs_sim* s);
 
 // ---- rounds.hip

@@ -37,6 +37,13 @@ __device__ __forceinline__ VT omit_fill(uint32_t rule) {
     return rule == 0 ? VT(0) : (VT)__builtin_huge_val();
 }
 
+// DESIGN.md §9 link schedules: one column group's four availability masks against the round's
+// phase bit (1u << (r mod period), unsigned: period 32 uses bit 31); bit k of the result is set
+// when column k of the group is down in this round.
+__device__ __forceinline__ uint32_t down_bits(uint4 m, uint32_t phase) {
+    return ((m.x & phase) ? 0u : 1u) | ((m.y & phase) ? 0u : 2u) | ((m.z & phase) ? 0u : 4u) | ((m.w & phase) ? 0u : 8u);
+}
+
 // DESIGN.md §9 bounded delay: sender j's value as delivered on slot s in round r, given the
 // slot's DELAY draw w: x_j^{r - min(r, w mod (D + 1))}.
 template <typename VT = double>

@@ -123,7 +123,9 @@ __device__ __forceinline__ VT generic_entry(const RoundArgs& a, uint32_t lb, uin
     }
     if (self) return xi;
     const uint32_t stj = stv ? stv[j] : kHonest;
-    const bool dropped = mp.thr && draw(mp.key, kStreamDrop, bG, r, slot) < mp.thr;
+    // (a.avail: a link schedule, CSR handles of rule WEIGHTED only here: a down slot is missing as a dropped one)
+    const bool dropped = (mp.thr && draw(mp.key, kStreamDrop, bG, r, slot) < mp.thr) ||
+                         (a.avail && !(a.avail[slot] & a.phase));
     const VT xj = a.delay ? delayed_x<VT>(a, lb, r, draw(mp.key, kStreamDelay, b, r, slot), j) : x[j];
     bool miss;
     const VT v = resolve_entry_m(mp, stj, xj, xi, dropped, b, r, i, slot, lo, hi, miss);
@@ -220,7 +222,9 @@ __global__ __launch_bounds__(BLK) void k_round_generic(const RoundArgs a, uint32
             VT pe = VT(0), ze = VT(0);
             if (e < m) {
                 const uint64_t slot = rp + e - 1;   // (entry 0 has no slot)
-                const bool dropped = e != 0 && mp.thr && draw(mp.key, kStreamDrop, bG, a.r, slot) < mp.thr;
+                // (a.avail: a link schedule; a slot that is down in this round is dropped)
+                const bool dropped = e != 0 && ((mp.thr && draw(mp.key, kStreamDrop, bG, a.r, slot) < mp.thr) ||
+                                                (a.avail && !(a.avail[slot] & a.phase)));
                 if (lk && e != 0) {
                     const VT wt = we[slot];
                     const V2 v = pin[a.colidx[slot]];

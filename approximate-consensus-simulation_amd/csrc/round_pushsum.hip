@@ -35,7 +35,10 @@ struct PsVec<double> {
     using pair = double2;
 };
 
-template <int D, typename VT>
+// SCHED ("Link schedules"): with each weight group come the group's four
+// availability masks (a.avell, the weights' order); a slot that is down in this round is gone like
+// a dropped one.
+template <int D, typename VT, bool SCHED>
 __global__ __launch_bounds__(kRegularBlock) void k_round_pushsum(const RoundArgs a) {
     static_assert(D % 4 == 0, "compiled widths are multiples of 4");
     constexpr int M = D + 1;
@@ -98,13 +101,18 @@ __global__ __launch_bounds__(kRegularBlock) void k_round_pushsum(const RoundArgs
         for (int q = 0; q < NQ; ++q) {
             W4 ww;
             ww.x = ww.y = ww.z = ww.w = VT(0);
-            if ((uint32_t)q < nqs) ww = wp[q * 64];
+            uint32_t down = 0;   // SCHED: bit k set = column 4q + k's slot is down in round r
+            if ((uint32_t)q < nqs) {
+                ww = wp[q * 64];
+                if (SCHED) down = down_bits(reinterpret_cast<const uint4*>(a.avell)[g0 + q * 64], a.phase);
+            }
             const VT wq[4] = {ww.x, ww.y, ww.z, ww.w};
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int t = 4 * q + k;
                 bool gone = (uint32_t)t >= dg;   // absent column: +0.0 in both sums
                 if (!gone && mp.thr) gone = draw(mp.key, kStreamDrop, bG, r, rp + t) < mp.thr;
+                if (SCHED) gone = gone || ((down >> k) & 1u);
                 ps[1 + t] = gone ? VT(0) : wq[k] * ps[1 + t] + VT(0);
                 pz[1 + t] = gone ? VT(0) : wq[k] * pz[1 + t] + VT(0);
             }
@@ -180,13 +188,17 @@ hipError_t launch_round_pushsum(const RoundArgs& a, uint64_t B, uint32_t nblk_fa
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)nblk_fast, (unsigned)B);
     const dim3 block(kRegularBlock);
-#define X(DD)                                                                       \
-    if (a.d == DD) {                                                                \
-        if (a.f32)                                                                  \
-            hipLaunchKernelGGL((k_round_pushsum<DD, float>), grid, block, 0, s, a);  \
-        else                                                                        \
-            hipLaunchKernelGGL((k_round_pushsum<DD, double>), grid, block, 0, s, a); \
-        return hipGetLastError();                                                   \
+#define X(DD)                                                                              \
+    if (a.d == DD) {                                                                       \
+        if (a.avell && a.f32)                                                              \
+            hipLaunchKernelGGL((k_round_pushsum<DD, float, true>), grid, block, 0, s, a);   \
+        else if (a.avell)                                                                  \
+            hipLaunchKernelGGL((k_round_pushsum<DD, double, true>), grid, block, 0, s, a);  \
+        else if (a.f32)                                                                    \
+            hipLaunchKernelGGL((k_round_pushsum<DD, float, false>), grid, block, 0, s, a);  \
+        else                                                                               \
+            hipLaunchKernelGGL((k_round_pushsum<DD, double, false>), grid, block, 0, s, a); \
+        return hipGetLastError();                                                          \
     }
     ACS_PUSHSUM_WIDTHS(X)
 #undef X

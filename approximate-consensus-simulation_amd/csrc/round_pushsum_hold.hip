@@ -32,7 +32,10 @@ namespace acs {
 __device__ __forceinline__ bool same_bits(double u, double v) { return __double_as_longlong(u) == __double_as_longlong(v); }
 __device__ __forceinline__ bool same_bits(float u, float v) { return __float_as_uint(u) == __float_as_uint(v); }
 
-template <int D, typename VT>
+// SCHED ("Link schedules"): with each weight group come the group's four
+// availability masks (a.avell, the weights' order); a slot that is down in this round takes the
+// dropped branch, so its mass waits on the link until the slot is up again.
+template <int D, typename VT, bool SCHED>
 __global__ __launch_bounds__(kRegularBlock) void k_round_pushsum_hold(const RoundArgs a) {
     static_assert(D % 4 == 0, "compiled widths are multiples of 4");
     constexpr int M = D + 1;
@@ -97,7 +100,11 @@ __global__ __launch_bounds__(kRegularBlock) void k_round_pushsum_hold(const Roun
         for (int q = 0; q < NQ; ++q) {
             W4 ww;
             ww.x = ww.y = ww.z = ww.w = VT(0);
-            if ((uint32_t)q < nqs) ww = wp[q * 64];
+            uint32_t down = 0;   // SCHED: bit k set = column 4q + k's slot is down in round r
+            if ((uint32_t)q < nqs) {
+                ww = wp[q * 64];
+                if (SCHED) down = down_bits(reinterpret_cast<const uint4*>(a.avell)[g0 + q * 64], a.phase);
+            }
             const VT wq[4] = {ww.x, ww.y, ww.z, ww.w};
             V2 l[4];   // the group's links, taken with its weights
 #pragma unroll
@@ -113,6 +120,7 @@ __global__ __launch_bounds__(kRegularBlock) void k_round_pushsum_hold(const Roun
                 const VT kn = l[k].y + (wq[k] * pz[1 + t] + VT(0));
                 bool dropped = false;
                 if (here && mp.thr) dropped = draw(mp.key, kStreamDrop, bG, r, rp + t) < mp.thr;
+                if (SCHED) dropped = dropped || (here && ((down >> k) & 1u));
                 ps[1 + t] = here && !dropped ? hn : VT(0);
                 pz[1 + t] = here && !dropped ? kn : VT(0);
                 V2 keep;
@@ -142,13 +150,17 @@ hipError_t launch_round_pushsum_hold(const RoundArgs& a, uint64_t B, uint32_t nb
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)nblk_fast, (unsigned)B);
     const dim3 block(kRegularBlock);
-#define X(DD)                                                                            \
-    if (a.d == DD) {                                                                     \
-        if (a.f32)                                                                       \
-            hipLaunchKernelGGL((k_round_pushsum_hold<DD, float>), grid, block, 0, s, a);  \
-        else                                                                             \
-            hipLaunchKernelGGL((k_round_pushsum_hold<DD, double>), grid, block, 0, s, a); \
-        return hipGetLastError();                                                        \
+#define X(DD)                                                                                   \
+    if (a.d == DD) {                                                                            \
+        if (a.avell && a.f32)                                                                   \
+            hipLaunchKernelGGL((k_round_pushsum_hold<DD, float, true>), grid, block, 0, s, a);   \
+        else if (a.avell)                                                                       \
+            hipLaunchKernelGGL((k_round_pushsum_hold<DD, double, true>), grid, block, 0, s, a);  \
+        else if (a.f32)                                                                         \
+            hipLaunchKernelGGL((k_round_pushsum_hold<DD, float, false>), grid, block, 0, s, a);  \
+        else                                                                                    \
+            hipLaunchKernelGGL((k_round_pushsum_hold<DD, double, false>), grid, block, 0, s, a); \
+        return hipGetLastError();                                                               \
     }
     ACS_PUSHSUM_HOLD_WIDTHS(X)
 #undef X

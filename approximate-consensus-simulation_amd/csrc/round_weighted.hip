@@ -30,7 +30,12 @@ struct WVec4<double> {
     using type = double4;
 };
 
-template <int D, typename VT>
+// SCHED ("Link schedules"): beside each weight group the lane loads the group's four
+// availability masks (a.avell, the weights' order), 16 B per lane, predicated like the weight load.
+// Once all groups are issued the masks are reduced to one bit per column, set when the slot is down
+// in this round (so they are dead before the gathers); a down slot's message is missing exactly as
+// a dropped one.
+template <int D, typename VT, bool SCHED>
 __global__ __launch_bounds__(kRegularBlock) void k_round_weighted(const RoundArgs a) {
     static_assert(D % 4 == 0, "compiled widths are multiples of 4");
     constexpr int M = D + 1;
@@ -67,14 +72,17 @@ __global__ __launch_bounds__(kRegularBlock) void k_round_weighted(const RoundArg
             uint32_t col[D];
             VT w[M], p[M];
             w[0] = reinterpret_cast<const VT*>(a.wself)[i];
+            uint4 mk[SCHED ? NQ : 1];   // SCHED: the groups' masks, reduced to one bit per column below
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
                 uint4 c = make_uint4(kEllNone, kEllNone, kEllNone, kEllNone);
                 W4 ww;
                 ww.x = ww.y = ww.z = ww.w = VT(0);
+                if constexpr (SCHED) mk[q] = make_uint4(0u, 0u, 0u, 0u);
                 if ((uint32_t)q < nqs) {   // groups past the slice's width are not loaded
                     c = cp[q * 64];
                     ww = wp[q * 64];
+                    if constexpr (SCHED) mk[q] = reinterpret_cast<const uint4*>(a.avell)[g0 + q * 64];
                 }
                 col[4 * q + 0] = c.x;
                 col[4 * q + 1] = c.y;
@@ -84,6 +92,13 @@ __global__ __launch_bounds__(kRegularBlock) void k_round_weighted(const RoundArg
                 w[1 + 4 * q + 1] = ww.y;
                 w[1 + 4 * q + 2] = ww.z;
                 w[1 + 4 * q + 3] = ww.w;
+            }
+            // after the loads, not inside their loop: a reduction there would make every group's loads
+            // wait for the group before it (bit t set = column t's slot is down in round r)
+            uint32_t down = 0;
+            if constexpr (SCHED) {
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) down |= down_bits(mk[q], a.phase) << (4 * q);
             }
             const MsgParams& mp = a.mp;
             const uint32_t b = (uint32_t)(mp.inst_offset + lb);
@@ -110,7 +125,8 @@ __global__ __launch_bounds__(kRegularBlock) void k_round_weighted(const RoundArg
                 VT u = xi;
                 if (!gone) {
                     const uint64_t s = rp + t;
-                    const bool dropped = mp.thr && draw(mp.key, kStreamDrop, bG, r, s) < mp.thr;
+                    bool dropped = mp.thr && draw(mp.key, kStreamDrop, bG, r, s) < mp.thr;
+                    if (SCHED) dropped = dropped || ((down >> t) & 1u);
                     bool miss;
                     u = resolve_entry_m(mp, sj[t], xj[t], xi, dropped, b, r, i, s, lo, hi, miss);
                     gone = mp.omit && miss;   // SELF: the entry takes x_i and keeps its weight
@@ -129,6 +145,24 @@ __global__ __launch_bounds__(kRegularBlock) void k_round_weighted(const RoundArg
         }
     }
     block_minmax_store<kRegularBlock>(mn, mx, a.partial + (uint64_t)lb * a.nblk + blockIdx.x);
+}
+
+// a link schedule's masks, slot order -> the weights' order; 0 in absent columns and hub rows (never read)
+__global__ __launch_bounds__(256) void k_avail_to_ell(const uint64_t* __restrict__ rowptr, const uint32_t* __restrict__ avail,
+                                                      const uint8_t* __restrict__ deg, uint64_t N, uint32_t d,
+                                                      uint32_t* __restrict__ avell) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const uint64_t rp = rowptr[i];
+    const uint32_t dg = deg[i] == kDegHub ? 0u : deg[i];
+    for (uint32_t t = 0; t < d; ++t)
+        avell[(((i >> 6) * (d >> 2) + (t >> 2)) * 64 + (i & 63)) * 4 + (t & 3)] = t < dg ? avail[rp + t] : 0u;
+}
+
+hipError_t launch_avail_to_ell(const uint64_t* rowptr, const uint32_t* avail, const uint8_t* deg, uint64_t N,
+                               uint32_t d, uint32_t* avell, hipStream_t s) {
+    hipLaunchKernelGGL(k_avail_to_ell, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, rowptr, avail, deg, N, d, avell);
+    return hipGetLastError();
 }
 
 // wedge (slot order) -> the ELL's slice / group / lane order, +0.0 in absent columns; hub rows keep
@@ -171,13 +205,17 @@ hipError_t launch_round_weighted(const RoundArgs& a, uint64_t B, uint32_t nblk_f
     if (!a.deg || !a.sw || !a.ell || !a.well || !a.wself || !a.rowptr) return hipErrorInvalidValue;
     const dim3 grid((unsigned)nblk_fast, (unsigned)B);
     const dim3 block(kRegularBlock);
-#define X(DD)                                                                        \
-    if (a.d == DD) {                                                                 \
-        if (a.f32)                                                                   \
-            hipLaunchKernelGGL((k_round_weighted<DD, float>), grid, block, 0, s, a);  \
-        else                                                                         \
-            hipLaunchKernelGGL((k_round_weighted<DD, double>), grid, block, 0, s, a); \
-        return hipGetLastError();                                                    \
+#define X(DD)                                                                               \
+    if (a.d == DD) {                                                                        \
+        if (a.avell && a.f32)                                                               \
+            hipLaunchKernelGGL((k_round_weighted<DD, float, true>), grid, block, 0, s, a);   \
+        else if (a.avell)                                                                   \
+            hipLaunchKernelGGL((k_round_weighted<DD, double, true>), grid, block, 0, s, a);  \
+        else if (a.f32)                                                                     \
+            hipLaunchKernelGGL((k_round_weighted<DD, float, false>), grid, block, 0, s, a);  \
+        else                                                                                \
+            hipLaunchKernelGGL((k_round_weighted<DD, double, false>), grid, block, 0, s, a); \
+        return hipGetLastError();                                                           \
     }
     ACS_WEIGHTED_WIDTHS(X)
 #undef X

@@ -153,6 +153,11 @@ static RoundArgs round_args(acs_sim* s, uint32_t r) {
     a.wself = s->wself;
     a.wedge = s->wedge;
     a.well = s->well;
+    if (s->sched) {   // (the phase follows the round index, also after acs_set_state(round, ...))
+        a.avail = s->avail;
+        a.avell = s->avell;
+        a.phase = 1u << (r % s->period);
+    }
     if (s->pushsum) {
         a.pin = pairs_at(s, r);
         a.pout = pairs_at(s, r + 1);

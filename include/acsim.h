@@ -30,7 +30,9 @@ extern "C" {
                                4: ACS_RULE_WEIGHTED, acs_create_csr_weighted, acs_get_weights
                                   (still 4: ACS_RULE_PUSHSUM and acs_get / acs_set_pushsum_state are
                                   additions; acs_config and every older symbol are unchanged;
-                                  likewise ACS_MISSING_HOLD and acs_get / acs_set_pushsum_links) */
+                                  likewise ACS_MISSING_HOLD and acs_get / acs_set_pushsum_links;
+                                  likewise ACS_SCHEDULE_MAX_PERIOD, acs_create_csr_scheduled and
+                                  acs_get_link_schedule) */
 
 /* status codes */
 #define ACS_OK            0
@@ -209,6 +211,26 @@ int acs_create_csr_weighted(const acs_config* cfg, const uint64_t* rowptr, const
  * n = N values into w_self_out, nnz = rowptr[N] values into w_edge_out.  Handles of
  * acs_create_csr_weighted only (rules WEIGHTED and PUSHSUM). */
 int acs_get_weights(struct acs_sim* sim, double* w_self_out, uint64_t n, double* w_edge_out, uint64_t nnz);
+
+/* DESIGN.md §9 ("Link schedules"): acs_create_csr_weighted on a time-varying graph.  A link
+ * schedule is a period P, 1 <= P <= ACS_SCHEDULE_MAX_PERIOD, and one mask per CSR slot, shared by all
+ * instances: bit p (p < P) of avail[slot] is set when the link on that slot is up in every round r
+ * with r mod P == p (r: the instance's own round index, which continues across acs_set_state and
+ * acs_set_pushsum_state).  Bits at positions >= P must be zero; avail[slot] == 0 is a dead link.
+ * A message on a slot that is down in round r is missing exactly as a dropped one: WEIGHTED / SELF
+ * takes x_i and keeps the weight, WEIGHTED / OMIT leaves the entry out, PUSHSUM / OMIT loses the
+ * mass, PUSHSUM / HOLD keeps it on the link until the slot is up again (the mean-preserving choice).
+ * With delay_max > 0 (WEIGHTED) the availability tested is that of the delivery round.
+ * Checked on the host before any device call: period outside 1..32, a null avail or a bit at a
+ * position >= period (ACS_EINVAL, naming the first offending slot); a rule other than WEIGHTED or
+ * PUSHSUM (ACS_EUNSUPPORTED); PUSHSUM with missing_policy = SELF and a slot that is not up in every
+ * phase (ACS_EINVAL); and every check of acs_create_csr_weighted. */
+#define ACS_SCHEDULE_MAX_PERIOD 32
+int acs_create_csr_scheduled(const acs_config* cfg, const uint64_t* rowptr, const uint32_t* colidx,
+                             const double* w_self, const double* w_edge,
+                             uint32_t period, const uint32_t* avail, int device, struct acs_sim** out);
+/* period into *period_out, nnz masks in slot order into avail_out; ACS_EINVAL on an unscheduled handle */
+int acs_get_link_schedule(struct acs_sim* sim, uint32_t* period_out, uint32_t* avail_out, uint64_t nnz);
 
 /* §8(e) node partitioning of ONE RANDOM_REGULAR instance over n_ranks GPUs (cfg5), one process
  * (or thread) per GPU.  Rank r owns the 64-aligned row block [r*R, (r+1)*R) ∩ [0, N),
