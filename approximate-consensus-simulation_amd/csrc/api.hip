@@ -524,7 +524,7 @@ int acs_get_neighbors(acs_sim* s, uint32_t* out, uint64_t n) {
     HIP_TRY(e);
     for (uint64_t i = 0; i < s->N; ++i)
         for (uint32_t t = 0; t < s->d; ++t)
-            out[i * s->d + t] = h[(((i >> 6) * (s->dp >> 2) + (t >> 2)) * 64 + (i & 63)) * 4 + (t & 3)];
+            out[i * s->d + t] = h[ell_slot(i, s->dp, t)];
     return ACS_OK;
 }
 

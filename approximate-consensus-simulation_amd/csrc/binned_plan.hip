@@ -27,7 +27,7 @@ struct BinGeom {
 };
 
 __device__ __forceinline__ uint32_t ell_at(const uint32_t* ell, uint64_t i, uint32_t t, uint32_t dp) {
-    return ell[(((i >> 6) * (dp >> 2) + (t >> 2)) * 64 + (i & 63)) * 4 + (t & 3)];
+    return ell[ell_slot(i, dp, t)];
 }
 
 __global__ __launch_bounds__(256) void k_bin_keys(const uint32_t* __restrict__ ell, uint64_t E, BinGeom G, int level,

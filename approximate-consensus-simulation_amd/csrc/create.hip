@@ -2,6 +2,7 @@
 // selection, HBM buffer ownership, graph / plan construction and release.  create_impl runs the
 // creation stages in order; each returns an ACS code (message through fail) and create_impl
 // releases the handle when one fails.  SURVEY §8(b), §8(e).
+#include "csr_lane.hpp"
 #include "handle.hpp"
 #include "sched_check.hpp"
 
@@ -238,11 +239,10 @@ void release(acs_sim* s) {
 // CSR on the register / binned paths (§8(f) row 1): the smallest compiled degree D >= the
 // largest row with the config's (t, rule), 0 if none (the generic kernel then runs).
 // (rules WEIGHTED and PUSHSUM have their own per-lane kernels, k_round_weighted<D> and
-// k_round_pushsum<D> (under HOLD k_round_pushsum_hold<D>), over the same padded rows; WEIGHTED also
-// a binned phase B, decide_binned)
+// k_round_pushsum<D> (under HOLD its HOLD instantiation), over the same padded rows and so of the
+// same widths, csr_lane.hpp; WEIGHTED also a binned phase B, decide_binned)
 static bool csr_width_compiled(uint32_t d, uint32_t t, uint32_t rule) {
-    if (rule == ACS_RULE_WEIGHTED) return t == 0 && weighted_fast_supported(d);
-    if (rule == ACS_RULE_PUSHSUM) return t == 0 && pushsum_fast_supported(d);
+    if (rule == ACS_RULE_WEIGHTED || rule == ACS_RULE_PUSHSUM) return t == 0 && csr_lane_fast_supported(d);
     return regular_fast_supported(d, t, rule);
 }
 
@@ -667,6 +667,7 @@ static std::string kernel_name_of(const acs_sim* s) {
         if (s->bin_sb != kBinSB) nm += " sb" + std::to_string(s->bin_sb);
     } else if (s->csr_var) {
         const std::string w = "<" + std::to_string(s->d) + (s->sched ? ",csr,sched>" : ",csr>");   // (SCHED instantiations)
+        // (k_round_pushsum_hold: the reported name of k_round_pushsum's HOLD = true instantiation)
         nm = s->hold     ? "k_round_pushsum_hold" + w
            : s->pushsum  ? "k_round_pushsum" + w
            : s->weighted ? "k_round_weighted" + w

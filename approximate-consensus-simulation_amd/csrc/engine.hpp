@@ -27,6 +27,7 @@
 
 #include "binned_select.hpp"
 #include "csr_check.hpp"
+#include "ell_row.hpp"
 #include "spec.hpp"
 
 namespace acs {
@@ -206,24 +207,23 @@ hipError_t launch_round_regular(const RoundArgs& a, uint64_t B, bool clean, hipS
 constexpr uint32_t kRegularBlock = 256;
 
 // Rule WEIGHTED on a CSR graph (round_weighted.hip): one lane per receiver over the padded ELL of
-// width d in {4, 8, 16, 32} and the weight array beside it; hub rows (kDegHub) are skipped.
-bool weighted_fast_supported(uint32_t d);
+// a compiled width d (csr_lane.hpp: csr_lane_fast_supported) and the weight array beside it; hub
+// rows (kDegHub) are skipped.
 // nblk_fast: the kernel's own blocks (kRegularBlock rows each; hub rows' partial slots follow them)
 hipError_t launch_round_weighted(const RoundArgs& a, uint64_t B, uint32_t nblk_fast, hipStream_t s);
-// wedge (CSR slot order) -> well (the ELL's order) for the rows deg[] does not mark as hubs
+// (setup.hip) wedge (CSR slot order) -> well (the ELL's order) for the rows deg[] does not mark as hubs
 hipError_t launch_weights_to_ell(const uint64_t* rowptr, const void* wedge, const uint8_t* deg, uint64_t N,
                                  uint32_t d, bool f32, void* well, hipStream_t s);
-// a link schedule's masks, slot order -> the same order (0 in absent columns and hub rows)
+// (setup.hip) a link schedule's masks, slot order -> the same order (0 in absent columns and hub rows)
 hipError_t launch_avail_to_ell(const uint64_t* rowptr, const uint32_t* avail, const uint8_t* deg, uint64_t N,
                                uint32_t d, uint32_t* avell, hipStream_t s);
 
 // Rule PUSHSUM on a CSR graph (round_pushsum.hip): one lane per receiver over the same padded ELL
 // and weight array, a pair gather per sender; hub rows are skipped (k_round_generic's rule-6 branch).
-bool pushsum_fast_supported(uint32_t d);
-hipError_t launch_round_pushsum(const RoundArgs& a, uint64_t B, uint32_t nblk_fast, hipStream_t s);
-// The same under missing_policy = HOLD (round_pushsum_hold.hip): a dropped message's mass stays on
-// its link (a.lnk, updated in place) and arrives with the next message that gets through.
-hipError_t launch_round_pushsum_hold(const RoundArgs& a, uint64_t B, uint32_t nblk_fast, hipStream_t s);
+// hold: the handle runs missing_policy = HOLD (the kernel's HOLD instantiation): a dropped message's
+// mass stays on its link (a.lnk, updated in place) and arrives with the next message that gets
+// through.  hipErrorInvalidValue unless a.lnk is set exactly when hold is.
+hipError_t launch_round_pushsum(const RoundArgs& a, bool hold, uint64_t B, uint32_t nblk_fast, hipStream_t s);
 // pairs[k] = (x[k], 1) for n values (create, acs_set_state)
 hipError_t launch_pushsum_fill(const void* x, void* pairs, uint64_t n, bool f32, hipStream_t s);
 // x[k] = s / z where z > 0, else s (acs_set_pushsum_state)

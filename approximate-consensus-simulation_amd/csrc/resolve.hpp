@@ -44,6 +44,12 @@ __device__ __forceinline__ uint32_t down_bits(uint4 m, uint32_t phase) {
     return ((m.x & phase) ? 0u : 1u) | ((m.y & phase) ? 0u : 2u) | ((m.z & phase) ? 0u : 4u) | ((m.w & phase) ? 0u : 8u);
 }
 
+// The message on CSR / ELL slot `slot` is missing in round r before any fault is looked at: dropped
+// (§A.5), or the slot is down in this round under a link schedule (a.avail, slot order).
+__device__ __forceinline__ bool slot_missing(const RoundArgs& a, const MsgParams& mp, uint32_t bG, uint32_t r, uint64_t slot) {
+    return (mp.thr && draw(mp.key, kStreamDrop, bG, r, slot) < mp.thr) || (a.avail && !(a.avail[slot] & a.phase));
+}
+
 // DESIGN.md §9 bounded delay: sender j's value as delivered on slot s in round r, given the
 // slot's DELAY draw w: x_j^{r - min(r, w mod (D + 1))}.
 template <typename VT = double>

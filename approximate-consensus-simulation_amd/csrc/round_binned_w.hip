@@ -87,6 +87,7 @@ __global__ __launch_bounds__(kBinSB, D == 32 ? 2 : 1) void k_bin_gather_w(const 
         bin_dma_runs(tb, w * nrun / NW, (w + 1) * nrun / NW, stage, raw);
     // the weights, in flight beside the run copies: group q of the lane's row, only below deg(i)
     {
+        // (+ ell_group0(i, NQ), ell_row.hpp, as two offsets: added as one the kernel compiles to other code)
         const double4* wp = reinterpret_cast<const double4*>(a.well) + (uint64_t)(i >> 6) * (NQ * 64) + (i & 63);
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {

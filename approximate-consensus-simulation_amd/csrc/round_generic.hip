@@ -7,7 +7,6 @@
 // Used for the dense cfg2 shape (N = 1024 complete, t = 341) and any odd (d, t).
 #include <cstdlib>
 #include <mutex>
-#include <type_traits>
 
 #include "resolve.hpp"
 #include "sortnet.hpp"
@@ -118,14 +117,13 @@ __device__ __forceinline__ VT generic_entry(const RoundArgs& a, uint32_t lb, uin
     } else {                 // RANDOM_REGULAR: entry 0 self, entry 1+t from nbr(i,t)
         self = e == 0;
         const uint32_t t = e - 1;
-        j = self ? i : a.ell[(((uint64_t)(i >> 6) * (a.dp >> 2) + (t >> 2)) * 64 + (i & 63)) * 4 + (t & 3)];
+        j = self ? i : a.ell[ell_slot(i, a.dp, t)];
         slot = (uint64_t)i * a.d + t;
     }
     if (self) return xi;
     const uint32_t stj = stv ? stv[j] : kHonest;
-    // (a.avail: a link schedule, CSR handles of rule WEIGHTED only here: a down slot is missing as a dropped one)
-    const bool dropped = (mp.thr && draw(mp.key, kStreamDrop, bG, r, slot) < mp.thr) ||
-                         (a.avail && !(a.avail[slot] & a.phase));
+    // (a link schedule reaches here on CSR handles of rule WEIGHTED only)
+    const bool dropped = slot_missing(a, mp, bG, r, slot);
     const VT xj = a.delay ? delayed_x<VT>(a, lb, r, draw(mp.key, kStreamDelay, b, r, slot), j) : x[j];
     bool miss;
     const VT v = resolve_entry_m(mp, stj, xj, xi, dropped, b, r, i, slot, lo, hi, miss);
@@ -210,11 +208,11 @@ __global__ __launch_bounds__(BLK) void k_round_generic(const RoundArgs a, uint32
         // PUSHSUM (CSR rows, no faults, no delays): ps_e = (w_e * s_e) + 0.0 in one LDS
         // half and pz_e = (w_e * z_e) + 0.0 in the other, one entry-order tree sum each, no
         // normalisation; a dropped message (and the padding past m) adds +0.0 to both.  z' = 0 keeps x_i.
-        using V2 = typename std::conditional<sizeof(VT) == 4, float2, double2>::type;
+        using V2 = typename EllVec<VT>::pair;
         const VT* __restrict__ ws = reinterpret_cast<const VT*>(a.wself);
         const VT* __restrict__ we = reinterpret_cast<const VT*>(a.wedge);
         const V2* __restrict__ pin = reinterpret_cast<const V2*>(a.pin) + lb * N;
-        // missing_policy = HOLD (a.lnk, round_pushsum_hold.hip): the slot's held pair takes the product
+        // missing_policy = HOLD (a.lnk; k_round_pushsum's HOLD instantiation): the slot's held pair takes the product
         // (hn = h_e + a, kn = k_e + c); a delivered message contributes (hn, kn) and empties the link,
         // a dropped one contributes +0.0 and leaves (hn, kn) on it.  In place: one thread per slot.
         V2* lk = a.lnk ? reinterpret_cast<V2*>(a.lnk) + (uint64_t)lb * a.lnk_stride : nullptr;
@@ -222,9 +220,7 @@ __global__ __launch_bounds__(BLK) void k_round_generic(const RoundArgs a, uint32
             VT pe = VT(0), ze = VT(0);
             if (e < m) {
                 const uint64_t slot = rp + e - 1;   // (entry 0 has no slot)
-                // (a.avail: a link schedule; a slot that is down in this round is dropped)
-                const bool dropped = e != 0 && ((mp.thr && draw(mp.key, kStreamDrop, bG, a.r, slot) < mp.thr) ||
-                                                (a.avail && !(a.avail[slot] & a.phase)));
+                const bool dropped = e != 0 && slot_missing(a, mp, bG, a.r, slot);
                 if (lk && e != 0) {
                     const VT wt = we[slot];
                     const V2 v = pin[a.colidx[slot]];

@@ -17,37 +17,49 @@
 //   - x_i' = s_i' / z_i' (IEEE divide) where z_i' > 0, else x_i is kept; one pair store, one x store;
 //   - (min, max) of x^{r+1} reduced per block -> one partial (§A.8 epilogue).
 // Hub rows (deg[i] = kDegHub) are left to k_round_generic's rule-6 branch.
+//
+// HOLD = true is the rule under missing_policy = HOLD: robust ratio consensus by
+// running sums.  Mass that fails to cross a link is not lost: it waits on the link and arrives with
+// the next message that gets through.
+// Besides the (s, z) pair of every node, every CSR slot e = rowptr[i] + t of every instance holds a
+// pair (h_e, k_e) of the config dtype, [B][nnz] in slot order, +0.0 at round 0.  The lane's order
+// stays: ids, all pair gathers, then the weight groups.  With each weight group come the up to four
+// link pairs of its columns (loads predicated on t < deg(i): an absent column touches no link).
+// Per sender entry:
+//   a = (w_e * s_j) + 0.0, c = (w_e * z_j) + 0.0     as the plain rule: two roundings each, no FMA
+//   hn = h_e + a, kn = k_e + c                        one rounding each
+//   dropped = loss_p > 0 && draw(key, DROP, bG, r, e) < thr     the plain rule's draw
+//   delivered: the entry contributes (hn, kn), the link stores (+0.0, +0.0)
+//   dropped:   the entry contributes (+0.0, +0.0), the link stores (hn, kn)
+// The link is consumed as it arrives (ps[1 + t] takes hn or +0.0 in place), so nothing D-wide is
+// live beside ps and pz.  The update is in place: slot e is read and written by its receiver's lane
+// alone, in this launch alone, and a finished instance's blocks return before touching it.  A store
+// whose value equals, bit for bit, what was loaded is skipped (a delivered message on an empty
+// link: every link of a lossless run).
+// Hub rows take the same steps in k_round_generic's rule-6 branch when RoundArgs carries links.
+#include "csr_lane.hpp"
 #include "resolve.hpp"
 #include "rules.hpp"
 
 namespace acs {
 
-template <typename VT>
-struct PsVec;
-template <>
-struct PsVec<float> {
-    using w4 = float4;
-    using pair = float2;
-};
-template <>
-struct PsVec<double> {
-    using w4 = double4;
-    using pair = double2;
-};
+__device__ __forceinline__ bool same_bits(double u, double v) { return __double_as_longlong(u) == __double_as_longlong(v); }
+__device__ __forceinline__ bool same_bits(float u, float v) { return __float_as_uint(u) == __float_as_uint(v); }
 
 // SCHED ("Link schedules"): with each weight group come the group's four
 // availability masks (a.avell, the weights' order); a slot that is down in this round is gone like
-// a dropped one.
-template <int D, typename VT, bool SCHED>
+// a dropped one (HOLD: it takes the dropped branch, so its mass waits on the link until the slot is
+// up again).
+template <int D, typename VT, bool SCHED, bool HOLD>
 __global__ __launch_bounds__(kRegularBlock) void k_round_pushsum(const RoundArgs a) {
     static_assert(D % 4 == 0, "compiled widths are multiples of 4");
     constexpr int M = D + 1;
     constexpr int NQ = D / 4;
-    using W4 = typename PsVec<VT>::w4;
-    using V2 = typename PsVec<VT>::pair;
+    using W4 = typename EllVec<VT>::w4;
+    using V2 = typename EllVec<VT>::pair;
     const uint32_t lb = blockIdx.y;
     InstState* S = a.st + lb;
-    if (S->done) return;  // device-side early exit (uniform per block)
+    if (S->done) return;  // device-side early exit (uniform per block): a finished instance's links stay
 
     const uint64_t N = a.N;
     const VT* __restrict__ x = reinterpret_cast<const VT*>(a.xin) + lb * N;
@@ -58,12 +70,15 @@ __global__ __launch_bounds__(kRegularBlock) void k_round_pushsum(const RoundArgs
 
     double mn = kInf, mx = -kInf;   // exact for binary32 values too
     if (i < N && a.deg[i] != kDegHub) {
-        const uint64_t g0 = (uint64_t)(i >> 6) * (NQ * 64) + (i & 63);
+        const uint64_t g0 = ell_group0(i, NQ);
         const uint4* cp = reinterpret_cast<const uint4*>(a.ell) + g0;
         const W4* wp = reinterpret_cast<const W4*>(a.well) + g0;
         const uint32_t nqs = a.sw[i >> 6];   // uniform over the wave (one 64-row slice)
         const uint32_t dg = a.deg[i];
         const uint64_t rp = a.rowptr[i];
+        // HOLD: this row's links, slots rp .. rp + dg - 1 of instance lb (rp + dg <= nnz = a.lnk_stride).
+        // Formed here, before the id loads: inside the group loop it compiles to other code.
+        [[maybe_unused]] V2* lk = HOLD ? reinterpret_cast<V2*>(a.lnk) + (uint64_t)lb * a.lnk_stride + rp : nullptr;
         VT ps[M], pz[M];
         {
             uint32_t col[D];
@@ -91,7 +106,7 @@ __global__ __launch_bounds__(kRegularBlock) void k_round_pushsum(const RoundArgs
         }
         const VT xi = x[i];
         const VT w0 = reinterpret_cast<const VT*>(a.wself)[i];
-        ps[0] = w0 * ps[0] + VT(0);
+        ps[0] = w0 * ps[0] + VT(0);   // entry 0 has no link
         pz[0] = w0 * pz[0] + VT(0);
         const MsgParams& mp = a.mp;
         const uint32_t b = (uint32_t)(mp.inst_offset + lb);
@@ -107,20 +122,46 @@ __global__ __launch_bounds__(kRegularBlock) void k_round_pushsum(const RoundArgs
                 if (SCHED) down = down_bits(reinterpret_cast<const uint4*>(a.avell)[g0 + q * 64], a.phase);
             }
             const VT wq[4] = {ww.x, ww.y, ww.z, ww.w};
+            if constexpr (HOLD) {
+                V2 l[4];   // the group's links, taken with its weights
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int t = 4 * q + k;
-                bool gone = (uint32_t)t >= dg;   // absent column: +0.0 in both sums
-                if (!gone && mp.thr) gone = draw(mp.key, kStreamDrop, bG, r, rp + t) < mp.thr;
-                if (SCHED) gone = gone || ((down >> k) & 1u);
-                ps[1 + t] = gone ? VT(0) : wq[k] * ps[1 + t] + VT(0);
-                pz[1 + t] = gone ? VT(0) : wq[k] * pz[1 + t] + VT(0);
+                for (int k = 0; k < 4; ++k) {
+                    l[k].x = l[k].y = VT(0);
+                    if ((uint32_t)(4 * q + k) < dg) l[k] = lk[4 * q + k];
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int t = 4 * q + k;
+                    const bool here = (uint32_t)t < dg;   // absent column: +0.0 in both sums, no link
+                    const VT hn = l[k].x + (wq[k] * ps[1 + t] + VT(0));
+                    const VT kn = l[k].y + (wq[k] * pz[1 + t] + VT(0));
+                    bool dropped = false;
+                    if (here && mp.thr) dropped = draw(mp.key, kStreamDrop, bG, r, rp + t) < mp.thr;
+                    if (SCHED) dropped = dropped || (here && ((down >> k) & 1u));
+                    ps[1 + t] = here && !dropped ? hn : VT(0);
+                    pz[1 + t] = here && !dropped ? kn : VT(0);
+                    V2 keep;
+                    keep.x = dropped ? hn : VT(0);
+                    keep.y = dropped ? kn : VT(0);
+                    if (here && !(same_bits(keep.x, l[k].x) && same_bits(keep.y, l[k].y))) lk[t] = keep;
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int t = 4 * q + k;
+                    bool gone = (uint32_t)t >= dg;   // absent column: +0.0 in both sums
+                    if (!gone && mp.thr) gone = draw(mp.key, kStreamDrop, bG, r, rp + t) < mp.thr;
+                    if (SCHED) gone = gone || ((down >> k) & 1u);
+                    ps[1 + t] = gone ? VT(0) : wq[k] * ps[1 + t] + VT(0);
+                    pz[1 + t] = gone ? VT(0) : wq[k] * pz[1 + t] + VT(0);
+                }
             }
         }
         V2 o;
         o.x = tree_sum_const<M>(ps);
         o.y = tree_sum_const<M>(pz);
-        const VT res = o.y > VT(0) ? o.x / o.y : xi;   // z' = 0 (all mass lost on the way here): keep x_i
+        // z' = 0 (all mass lost on the way here, or under HOLD still on the links): keep x_i
+        const VT res = o.y > VT(0) ? o.x / o.y : xi;
         po[i] = o;
         xo[i] = res;
         mn = res;
@@ -132,10 +173,10 @@ __global__ __launch_bounds__(kRegularBlock) void k_round_pushsum(const RoundArgs
 // pairs[k] = (x[k], 1): round 0 of the rule, and acs_set_state
 template <typename VT>
 __global__ __launch_bounds__(256) void k_pushsum_fill(const VT* __restrict__ x,
-                                                      typename PsVec<VT>::pair* __restrict__ pairs, uint64_t n) {
+                                                      typename EllVec<VT>::pair* __restrict__ pairs, uint64_t n) {
     const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
-    typename PsVec<VT>::pair v;
+    typename EllVec<VT>::pair v;
     v.x = x[k];
     v.y = VT(1);
     pairs[k] = v;
@@ -143,11 +184,11 @@ __global__ __launch_bounds__(256) void k_pushsum_fill(const VT* __restrict__ x,
 
 // x[k] = s / z where z > 0, else s (acs_set_pushsum_state: the round's keep rule with nothing to keep)
 template <typename VT>
-__global__ __launch_bounds__(256) void k_pushsum_estimate(const typename PsVec<VT>::pair* __restrict__ pairs,
+__global__ __launch_bounds__(256) void k_pushsum_estimate(const typename EllVec<VT>::pair* __restrict__ pairs,
                                                           VT* __restrict__ x, uint64_t n) {
     const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
-    const typename PsVec<VT>::pair v = pairs[k];
+    const typename EllVec<VT>::pair v = pairs[k];
     x[k] = v.y > VT(0) ? v.x / v.y : v.x;
 }
 
@@ -174,35 +215,21 @@ hipError_t launch_pushsum_estimate(const void* pairs, void* x, uint64_t n, bool 
 }
 
 // ---------------------------------------------------------------------------- dispatch
-#define ACS_PUSHSUM_WIDTHS(X) X(4) X(8) X(16) X(32)
-
-bool pushsum_fast_supported(uint32_t d) {
-#define X(DD) if (d == DD) return true;
-    ACS_PUSHSUM_WIDTHS(X)
-#undef X
-    return false;
-}
-
-hipError_t launch_round_pushsum(const RoundArgs& a, uint64_t B, uint32_t nblk_fast, hipStream_t s) {
-    if (!a.deg || !a.sw || !a.ell || !a.well || !a.wself || !a.rowptr || !a.pin || !a.pout)
+hipError_t launch_round_pushsum(const RoundArgs& a, bool hold, uint64_t B, uint32_t nblk_fast, hipStream_t s) {
+    if (!a.deg || !a.sw || !a.ell || !a.well || !a.wself || !a.rowptr || !a.pin || !a.pout || hold != (a.lnk != nullptr))
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)nblk_fast, (unsigned)B);
     const dim3 block(kRegularBlock);
-#define X(DD)                                                                              \
-    if (a.d == DD) {                                                                       \
-        if (a.avell && a.f32)                                                              \
-            hipLaunchKernelGGL((k_round_pushsum<DD, float, true>), grid, block, 0, s, a);   \
-        else if (a.avell)                                                                  \
-            hipLaunchKernelGGL((k_round_pushsum<DD, double, true>), grid, block, 0, s, a);  \
-        else if (a.f32)                                                                    \
-            hipLaunchKernelGGL((k_round_pushsum<DD, float, false>), grid, block, 0, s, a);  \
-        else                                                                               \
-            hipLaunchKernelGGL((k_round_pushsum<DD, double, false>), grid, block, 0, s, a); \
-        return hipGetLastError();                                                          \
-    }
-    ACS_PUSHSUM_WIDTHS(X)
-#undef X
-    return hipErrorNotSupported;
+    const bool hit = csr_lane_select(a, [&](auto d, auto vt, auto sched) {
+        constexpr int DD = decltype(d)::value;
+        constexpr bool SCHED = decltype(sched)::value;
+        using VT = decltype(vt);
+        if (hold)
+            hipLaunchKernelGGL((k_round_pushsum<DD, VT, SCHED, true>), grid, block, 0, s, a);
+        else
+            hipLaunchKernelGGL((k_round_pushsum<DD, VT, SCHED, false>), grid, block, 0, s, a);
+    });
+    return hit ? hipGetLastError() : hipErrorNotSupported;
 }
 
 }  // namespace acs

@@ -51,6 +51,7 @@ __global__ __launch_bounds__(kRegularBlock) void k_round_regular(const RoundArgs
             }
         }
         if (active) {
+            // (+ ell_group0(li, NQ), ell_row.hpp, as two offsets: added as one the kernels compile to other code)
             const uint4* cp = reinterpret_cast<const uint4*>(a.ell) +
                               (uint64_t)(li >> 6) * (NQ * 64) + (li & 63);
             uint32_t col[D];

@@ -14,21 +14,11 @@
 //   - one IEEE divide (x_i is kept when the weight sum is 0, which only OMIT can produce), one store;
 //   - honest (min, max) of x^{r+1} reduced per block -> one partial (§A.8 epilogue).
 // Hub rows (deg[i] = kDegHub) are left to k_round_generic's rule-5 branch.
+#include "csr_lane.hpp"
 #include "resolve.hpp"
 #include "rules.hpp"
 
 namespace acs {
-
-template <typename VT>
-struct WVec4;
-template <>
-struct WVec4<float> {
-    using type = float4;
-};
-template <>
-struct WVec4<double> {
-    using type = double4;
-};
 
 // SCHED ("Link schedules"): beside each weight group the lane loads the group's four
 // availability masks (a.avell, the weights' order), 16 B per lane, predicated like the weight load.
@@ -40,7 +30,7 @@ __global__ __launch_bounds__(kRegularBlock) void k_round_weighted(const RoundArg
     static_assert(D % 4 == 0, "compiled widths are multiples of 4");
     constexpr int M = D + 1;
     constexpr int NQ = D / 4;
-    using W4 = typename WVec4<VT>::type;
+    using W4 = typename EllVec<VT>::w4;
     const uint32_t lb = blockIdx.y;
     InstState* S = a.st + lb;
     if (S->done) return;  // device-side early exit (uniform per block)
@@ -63,7 +53,7 @@ __global__ __launch_bounds__(kRegularBlock) void k_round_weighted(const RoundArg
             active = is_active(si, a.r);
         }
         if (active) {
-            const uint64_t g0 = (uint64_t)(i >> 6) * (NQ * 64) + (i & 63);
+            const uint64_t g0 = ell_group0(i, NQ);
             const uint4* cp = reinterpret_cast<const uint4*>(a.ell) + g0;
             const W4* wp = reinterpret_cast<const W4*>(a.well) + g0;
             const uint32_t nqs = a.sw[i >> 6];   // uniform over the wave (one 64-row slice)
@@ -147,79 +137,15 @@ __global__ __launch_bounds__(kRegularBlock) void k_round_weighted(const RoundArg
     block_minmax_store<kRegularBlock>(mn, mx, a.partial + (uint64_t)lb * a.nblk + blockIdx.x);
 }
 
-// a link schedule's masks, slot order -> the weights' order; 0 in absent columns and hub rows (never read)
-__global__ __launch_bounds__(256) void k_avail_to_ell(const uint64_t* __restrict__ rowptr, const uint32_t* __restrict__ avail,
-                                                      const uint8_t* __restrict__ deg, uint64_t N, uint32_t d,
-                                                      uint32_t* __restrict__ avell) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-    const uint64_t rp = rowptr[i];
-    const uint32_t dg = deg[i] == kDegHub ? 0u : deg[i];
-    for (uint32_t t = 0; t < d; ++t)
-        avell[(((i >> 6) * (d >> 2) + (t >> 2)) * 64 + (i & 63)) * 4 + (t & 3)] = t < dg ? avail[rp + t] : 0u;
-}
-
-hipError_t launch_avail_to_ell(const uint64_t* rowptr, const uint32_t* avail, const uint8_t* deg, uint64_t N,
-                               uint32_t d, uint32_t* avell, hipStream_t s) {
-    hipLaunchKernelGGL(k_avail_to_ell, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, rowptr, avail, deg, N, d, avell);
-    return hipGetLastError();
-}
-
-// wedge (slot order) -> the ELL's slice / group / lane order, +0.0 in absent columns; hub rows keep
-// an all-zero row (the fast kernel never reads it)
-template <typename VT>
-__global__ __launch_bounds__(256) void k_weights_to_ell(const uint64_t* __restrict__ rowptr, const VT* __restrict__ wedge,
-                                                        const uint8_t* __restrict__ deg, uint64_t N, uint32_t d,
-                                                        VT* __restrict__ well) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-    const uint64_t rp = rowptr[i];
-    const uint32_t dg = deg[i] == kDegHub ? 0u : deg[i];
-    for (uint32_t t = 0; t < d; ++t)
-        well[(((i >> 6) * (d >> 2) + (t >> 2)) * 64 + (i & 63)) * 4 + (t & 3)] = t < dg ? wedge[rp + t] : VT(0);
-}
-
-hipError_t launch_weights_to_ell(const uint64_t* rowptr, const void* wedge, const uint8_t* deg, uint64_t N,
-                                 uint32_t d, bool f32, void* well, hipStream_t s) {
-    const dim3 grid((unsigned)((N + 255) / 256));
-    if (f32)
-        hipLaunchKernelGGL(k_weights_to_ell<float>, grid, dim3(256), 0, s, rowptr, static_cast<const float*>(wedge), deg,
-                           N, d, static_cast<float*>(well));
-    else
-        hipLaunchKernelGGL(k_weights_to_ell<double>, grid, dim3(256), 0, s, rowptr, static_cast<const double*>(wedge),
-                           deg, N, d, static_cast<double*>(well));
-    return hipGetLastError();
-}
-
 // ---------------------------------------------------------------------------- dispatch
-#define ACS_WEIGHTED_WIDTHS(X) X(4) X(8) X(16) X(32)
-
-bool weighted_fast_supported(uint32_t d) {
-#define X(DD) if (d == DD) return true;
-    ACS_WEIGHTED_WIDTHS(X)
-#undef X
-    return false;
-}
-
 hipError_t launch_round_weighted(const RoundArgs& a, uint64_t B, uint32_t nblk_fast, hipStream_t s) {
     if (!a.deg || !a.sw || !a.ell || !a.well || !a.wself || !a.rowptr) return hipErrorInvalidValue;
     const dim3 grid((unsigned)nblk_fast, (unsigned)B);
     const dim3 block(kRegularBlock);
-#define X(DD)                                                                               \
-    if (a.d == DD) {                                                                        \
-        if (a.avell && a.f32)                                                               \
-            hipLaunchKernelGGL((k_round_weighted<DD, float, true>), grid, block, 0, s, a);   \
-        else if (a.avell)                                                                   \
-            hipLaunchKernelGGL((k_round_weighted<DD, double, true>), grid, block, 0, s, a);  \
-        else if (a.f32)                                                                     \
-            hipLaunchKernelGGL((k_round_weighted<DD, float, false>), grid, block, 0, s, a);  \
-        else                                                                                \
-            hipLaunchKernelGGL((k_round_weighted<DD, double, false>), grid, block, 0, s, a); \
-        return hipGetLastError();                                                           \
-    }
-    ACS_WEIGHTED_WIDTHS(X)
-#undef X
-    return hipErrorNotSupported;
+    const bool hit = csr_lane_select(a, [&](auto d, auto vt, auto sched) {
+        hipLaunchKernelGGL((k_round_weighted<decltype(d)::value, decltype(vt), decltype(sched)::value>), grid, block, 0, s, a);
+    });
+    return hit ? hipGetLastError() : hipErrorNotSupported;
 }
 
 }  // namespace acs

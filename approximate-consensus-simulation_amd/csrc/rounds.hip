@@ -327,10 +327,8 @@ static int enqueue_round(acs_sim* s, uint32_t r) {
             if (s->n_hub) ab.qhi = s->nblk_fast;   // the hub rows' partial slots are the generic kernel's
             HIP_TRY(launch_round_binned(s->bin, ab, s->clean, s->stream, s->fin_pending ? &s->fin_args : nullptr));
             s->fin_pending = false;
-        } else if (s->path == PATH_REGULAR && s->hold) {
-            HIP_TRY(launch_round_pushsum_hold(a, s->B, s->nblk_fast, s->stream));
         } else if (s->path == PATH_REGULAR && s->pushsum) {
-            HIP_TRY(launch_round_pushsum(a, s->B, s->nblk_fast, s->stream));
+            HIP_TRY(launch_round_pushsum(a, s->hold, s->B, s->nblk_fast, s->stream));
         } else if (s->path == PATH_REGULAR && s->weighted) {
             HIP_TRY(launch_round_weighted(a, s->B, s->nblk_fast, s->stream));
         } else if (s->path == PATH_REGULAR) {

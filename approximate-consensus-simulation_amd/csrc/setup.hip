@@ -53,7 +53,7 @@ template <int D>
 __global__ __launch_bounds__(256) void k_sort_ell_rows(uint32_t* ell, uint64_t N) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
-    uint4* cp = reinterpret_cast<uint4*>(ell) + (i >> 6) * (D / 4) * 64 + (i & 63);
+    uint4* cp = reinterpret_cast<uint4*>(ell) + ell_group0((uint32_t)i, D / 4);   // (ids are u32: N < 2^32)
     uint32_t v[D];
 #pragma unroll
     for (int q = 0; q < D / 4; ++q) {
@@ -77,6 +77,14 @@ hipError_t launch_sort_ell_rows(uint32_t* ell, uint64_t N, uint32_t d, hipStream
     return hipGetLastError();
 }
 
+// Row i of a slot-order array -> the ELL's slice / group / lane order (ell_row.hpp): column t < dg
+// takes src[rp + t], every other column of the row's d takes `fill`.
+template <typename T>
+__device__ __forceinline__ void row_to_ell(const T* __restrict__ src, uint64_t rp, uint32_t dg, uint64_t i, uint32_t d,
+                                           T fill, T* __restrict__ dst) {
+    for (uint32_t t = 0; t < d; ++t) dst[ell_slot(i, d, t)] = t < dg ? src[rp + t] : fill;
+}
+
 // §8(f) row 1: CSR rows as the padded ELL slice layout of the register / binned paths.
 __global__ __launch_bounds__(256) void k_csr_to_ell(const uint64_t* __restrict__ rowptr, const uint32_t* __restrict__ colidx,
                                                     uint64_t N, uint32_t d, uint32_t* __restrict__ ell,
@@ -88,8 +96,38 @@ __global__ __launch_bounds__(256) void k_csr_to_ell(const uint64_t* __restrict__
     const bool hub = dg64 > d;   // served by the generic kernel: an empty ELL row
     const uint32_t dg = hub ? 0u : (uint32_t)dg64;
     deg[i] = hub ? kDegHub : (uint8_t)dg;
-    for (uint32_t t = 0; t < d; ++t)
-        ell[(((i >> 6) * (d >> 2) + (t >> 2)) * 64 + (i & 63)) * 4 + (t & 3)] = t < dg ? colidx[rp + t] : kEllNone;
+    row_to_ell(colidx, rp, dg, i, d, kEllNone, ell);
+}
+
+// A per-slot array of the fast path's rows (the edge weights, a link schedule's masks) in the ELL's
+// own order, `fill` in absent columns; hub rows keep an all-fill row (the fast kernels never read it).
+template <typename T>
+__global__ __launch_bounds__(256) void k_slots_to_ell(const uint64_t* __restrict__ rowptr, const T* __restrict__ src,
+                                                      const uint8_t* __restrict__ deg, uint64_t N, uint32_t d, T fill,
+                                                      T* __restrict__ dst) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    row_to_ell(src, rowptr[i], deg[i] == kDegHub ? 0u : (uint32_t)deg[i], i, d, fill, dst);
+}
+
+template <typename T>
+static hipError_t launch_slots_to_ell(const uint64_t* rowptr, const T* src, const uint8_t* deg, uint64_t N, uint32_t d,
+                                      T fill, T* dst, hipStream_t s) {
+    hipLaunchKernelGGL(k_slots_to_ell<T>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, rowptr, src, deg, N, d, fill, dst);
+    return hipGetLastError();
+}
+
+// wedge (slot order) -> well, +0.0 in absent columns
+hipError_t launch_weights_to_ell(const uint64_t* rowptr, const void* wedge, const uint8_t* deg, uint64_t N,
+                                 uint32_t d, bool f32, void* well, hipStream_t s) {
+    if (f32) return launch_slots_to_ell(rowptr, static_cast<const float*>(wedge), deg, N, d, 0.0f, static_cast<float*>(well), s);
+    return launch_slots_to_ell(rowptr, static_cast<const double*>(wedge), deg, N, d, 0.0, static_cast<double*>(well), s);
+}
+
+// a link schedule's masks, slot order -> the weights' order; 0 in absent columns and hub rows (never read)
+hipError_t launch_avail_to_ell(const uint64_t* rowptr, const uint32_t* avail, const uint8_t* deg, uint64_t N,
+                               uint32_t d, uint32_t* avell, hipStream_t s) {
+    return launch_slots_to_ell(rowptr, avail, deg, N, d, 0u, avell, s);
 }
 
 // SELL-64 slice widths: 4-wide column groups used by the longest row of each 64-row slice
