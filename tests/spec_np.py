@@ -110,6 +110,41 @@ def tree_sum_rows(a: np.ndarray) -> np.ndarray:
     return w[..., 0]
 
 
+class RaggedTreeSum:
+    """§A.7 tree_sum of every row of a ragged matrix given as flat entries (row, position, value).
+
+    Row i holds width[i] entries.  The rows are grouped by the power of two >= width[i] and each group
+    is summed by tree_sum_rows at that width, instead of padding every row to the widest.  Bit for bit
+    the same sums: when a row is padded with +0.0 to a larger power of two, the upper half of every
+    level above the row's own is +0.0, and v + (+0.0) = v for every v that is not -0.0 (the callers
+    have no -0.0 summand), so those levels copy the row and the rest are the row's own levels.  A row
+    with no entry given sums to +0.0."""
+
+    def __init__(self, width):
+        width = np.asarray(width, dtype=np.int64)
+        P = np.ones_like(width)
+        while (P < width).any():
+            P[P < width] *= 2
+        self.n = width.size
+        self.P = P
+        self.local = np.zeros(self.n, dtype=np.int64)
+        self.members = {}
+        for p in np.unique(P):
+            idx = np.nonzero(P == p)[0]
+            self.local[idx] = np.arange(idx.size)
+            self.members[int(p)] = idx
+
+    def __call__(self, rows, pos, vals):
+        out = np.zeros(self.n, dtype=vals.dtype)
+        pe = self.P[rows]
+        for p, idx in self.members.items():
+            k = pe == p
+            a = np.zeros((idx.size, p), dtype=vals.dtype)
+            a[self.local[rows[k]], pos[k]] = vals[k]
+            out[idx] = tree_sum_rows(a)
+        return out
+
+
 def apply_rule(rule: int, t: int, S: np.ndarray, xi=None) -> np.ndarray:
     """§A.7 on rows of S (entry order preserved for AVERAGE); xi = receivers' own values (W-MSR)."""
     m = S.shape[1]

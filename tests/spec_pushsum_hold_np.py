@@ -21,7 +21,6 @@ from __future__ import annotations
 
 import numpy as np
 
-import spec_np as S
 from spec_pushsum_np import NpPushSumSim
 
 
@@ -73,11 +72,7 @@ class NpPushSumHoldSim(NpPushSumSim):
         pz = np.where(gone, ft(0), kn).astype(ft)
         self.h[lb] = np.where(gone, hn, ft(0))
         self.k[lb] = np.where(gone, kn, ft(0))
-        Ps = np.zeros((self.N, self.mmax), dtype=ft)
-        Pz = np.zeros((self.N, self.mmax), dtype=ft)
-        Ps[self.e_row, self.e_pos] = ps
-        Pz[self.e_row, self.e_pos] = pz
-        sn, zn = S.tree_sum_rows(Ps), S.tree_sum_rows(Pz)
+        sn, zn = self.row_sums(self.e_row, self.e_pos, ps), self.row_sums(self.e_row, self.e_pos, pz)
         with np.errstate(divide="ignore", invalid="ignore"):
             q = (sn / zn).astype(ft)
         self.kept[lb].append(int(np.count_nonzero(zn == 0)))

@@ -11,15 +11,14 @@ its; only the row update is restated here, from the spec:
     loss        a dropped message adds +0.0 to both sums (its mass is lost)
     fp32        every operation in binary32, subnormals included
 
-The products are laid out one receiver per row, padded with +0.0 to the widest row, for
-spec_np.tree_sum_rows; no summand is -0.0, so the padding leaves each row's stride-halving sums
-unchanged (the argument of spec_weighted_np).
+The products are laid out one receiver per row, padded with +0.0 to a power of two, for
+spec_np.tree_sum_rows (the parent's row_sums); no summand is -0.0, so the padding leaves each row's
+stride-halving sums unchanged (the argument of spec_weighted_np).
 """
 from __future__ import annotations
 
 import numpy as np
 
-import spec_np as S
 from spec_weighted_np import NpWeightedSim
 
 
@@ -56,11 +55,7 @@ class NpPushSumSim(NpWeightedSim):
         gone = miss[:, 0]
         ps = np.where(gone, ft(0), (self.e_w * s[self.e_j]).astype(ft) + ft(0)).astype(ft)
         pz = np.where(gone, ft(0), (self.e_w * z[self.e_j]).astype(ft) + ft(0)).astype(ft)
-        Ps = np.zeros((self.N, self.mmax), dtype=ft)
-        Pz = np.zeros((self.N, self.mmax), dtype=ft)
-        Ps[self.e_row, self.e_pos] = ps
-        Pz[self.e_row, self.e_pos] = pz
-        sn, zn = S.tree_sum_rows(Ps), S.tree_sum_rows(Pz)
+        sn, zn = self.row_sums(self.e_row, self.e_pos, ps), self.row_sums(self.e_row, self.e_pos, pz)
         with np.errstate(divide="ignore", invalid="ignore"):
             q = (sn / zn).astype(ft)
         self.kept[lb].append(int(np.count_nonzero(zn == 0)))

@@ -12,10 +12,11 @@ A subclass of spec_np.NpSim: topology, faults, drops, delays and the §A.6 resol
 
 All receivers are resolved in one `_values` call over the flat list of their entries (one entry
 per "row" of that call, so no draw is spent on padding), and the products and weights are then laid
-out one receiver per row, padded with +0.0 to the widest row, for spec_np.tree_sum_rows.  No
-summand is -0.0, so zeros past a row's end leave its stride-halving sums unchanged (the argument of
-spec_np.apply_rule_omit's masked windows): each row's result is that of tree sums over its own m_i
-entries.
+out one receiver per row, padded with +0.0 to a power of two, for spec_np.tree_sum_rows
+(spec_np.RaggedTreeSum: rows of like width together, so one 8192-entry hub row does not widen every
+other row).  No summand is -0.0, so zeros past a row's end leave its stride-halving sums unchanged
+(the argument of spec_np.apply_rule_omit's masked windows): each row's result is that of tree sums
+over its own m_i entries.
 """
 from __future__ import annotations
 
@@ -35,6 +36,7 @@ class NpWeightedSim(S.NpSim):
         N = self.N
         deg = np.diff(self.rowptr)
         self.mmax = int(deg.max(initial=0)) + 1
+        self.row_sums = S.RaggedTreeSum(deg + 1)   # the rows' tree sums, grouped by width
         own = np.arange(N, dtype=np.int64)
         edge_row = np.repeat(own, deg)
         nnz = edge_row.size
@@ -66,11 +68,7 @@ class NpWeightedSim(S.NpSim):
             gone = miss if self.omit else np.zeros_like(miss)
             w = np.where(gone, ft(0), self.e_w[E]).astype(ft)
             p = np.where(gone, ft(0), (w * V).astype(ft) + ft(0)).astype(ft)
-            P = np.zeros((self.N, self.mmax), dtype=ft)
-            W = np.zeros((self.N, self.mmax), dtype=ft)
-            P[rows, self.e_pos[E]] = p
-            W[rows, self.e_pos[E]] = w
-            num, den = S.tree_sum_rows(P), S.tree_sum_rows(W)
+            num, den = self.row_sums(rows, self.e_pos[E], p), self.row_sums(rows, self.e_pos[E], w)
             with np.errstate(divide="ignore", invalid="ignore"):
                 q = (num / den).astype(ft)
             self.zero_den += int(np.count_nonzero(active & (den == 0)))

@@ -1,5 +1,8 @@
 """Long randomized GPU-vs-oracle sweep (the strategies of tests/test_properties.py, not
-derandomized): python tools/fuzz_gpu.py [--examples 2000] [--seed S] [--which configs,csr,binned,partitions,resume,steps,hubs,dense]
+derandomized): python tools/fuzz_gpu.py [--examples 2000] [--seed S] [--which configs,csr,binned,partitions,resume,steps,hubs,dense,csr_rules]
+
+csr_rules draws tests/test_properties_csr_rules.py's strategy (rules "weighted" and "pushsum" on CSR
+graphs with hub rows, HOLD and link schedules) and checks the handle against the numpy restatement.
 
 Prints one line per strategy with the number of passing draws, or the falsifying example.
 """
@@ -67,6 +70,10 @@ def main():
 
     # complete graphs the persistent dense kernel serves (asserts the kernel; up to 2048 nodes)
     tests["dense"] = (T.test_gpu_dense_random_configs, "cfg", T.dense_configs(max_n=2048))
+
+    # rules "weighted" and "pushsum" (four rule / policy pairs, schedules, hub rows of every size class)
+    import test_properties_csr_rules as TC
+    tests["csr_rules"] = (TC.test_gpu_csr_rules_match_restatement_random_cases, "case", TC.csr_rule_cases())
     for name in a.which.split(","):
         if name not in tests:
             continue
