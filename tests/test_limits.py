@@ -5,9 +5,11 @@
   B·N > 2^31 batch whose sampled instances (fault set, x after two rounds) match the oracle run of
   that instance alone (instance_offset = its global id, SURVEY §A.1 counters).
 - Receivers with more than 8192 entries (complete graphs above 8192 nodes, CSR hubs): the big-m
-  generic path (round_generic.hip: global scratch, segmented radix sort, global stride-halving
-  sums), bit-exact against the oracle for every rule, OMIT, fp32, delay and several instances, with
-  forced small batches (ACSIM_BIG_CAP) as well.
+  generic path (round_generic.hip: global scratch, a per-receiver merge sort of 8192-entry LDS
+  chunks followed by merge-path passes in global memory, global stride-halving sums), bit-exact
+  against the oracle for every rule, OMIT, fp32, delay and several instances, with forced small
+  batches (ACSIM_BIG_CAP) as well.  These rows have two chunks and one pass; tests/test_gpu_big_rows.py
+  covers the other chunk counts, pass counts and tail widths.
 """
 import contextlib
 import os

@@ -196,6 +196,56 @@ def test_gpu_matches_oracle_random_csr(oracle_mod, case):
 
 
 @st.composite
+def big_row_cases(draw):
+    """A CSR graph with 1 to 4 rows on the big-m path (8193 .. 140 000 entries: sizes of
+    big_rows.BIG_M, which sit on k_big_sort's pass-count and tail-width boundaries, or any size) on
+    48 .. 3000 nodes, and a valid Config for it: (cfg, (rowptr, colidx)).  The other rows have d0 ..
+    d0 + 3 senders, d0 up to 2000 on few nodes, and the trim is drawn up to the smallest row's
+    limit, so trims reach the hundreds.  Rule, missing policy, loss, fault model, delays, instances
+    and dtype come from configs(); at most 4 rounds."""
+    from big_rows import BIG_M
+    d0 = draw(st.sampled_from([2, 5, 12, 33, 200, 2000]))
+    n = draw(st.integers(48, min(3000, max(48, 400000 // d0))))
+    rng = np.random.default_rng(draw(st.integers(0, 2 ** 32)))
+    deg = rng.integers(d0, d0 + 4, size=n)
+    sizes = draw(st.lists(st.one_of(st.sampled_from(BIG_M), st.integers(8193, 140000)), min_size=1, max_size=4))
+    deg[rng.permutation(n)[:len(sizes)]] = np.array(sizes) - 1
+    rowptr = np.concatenate([[0], np.cumsum(deg)]).astype(np.uint64)
+    colidx = rng.integers(0, n, size=int(rowptr[-1])).astype(np.uint32)
+    base = draw(configs())
+    tmax = d0 // 2   # m_i = deg(i) + 1 > 2t for every row
+    rule = draw(st.sampled_from(["trimmed", "midpoint", "dlpsw", "wmsr", "trimmed", "average"]))   # (average does not sort)
+    t = 0 if rule == "average" else draw(st.integers(1, tmax))
+    cfg = base.replace(topology="csr", n_nodes=n, degree=0, rule=rule, trim=t, n_instances=min(base.n_instances, 2),
+                       n_faulty=min(base.n_faulty, n // 4), max_rounds=min(base.max_rounds, 4))
+    return cfg, (rowptr, colidx)
+
+
+@pytest.mark.gpu
+@settings(max_examples=20, deadline=None, derandomize=True, database=None,
+          suppress_health_check=[HealthCheck.too_slow, HealthCheck.data_too_large])
+@given(case=big_row_cases())
+def test_gpu_matches_oracle_random_big_rows(oracle_mod, case):
+    """Rows above 8192 entries (k_big_resolve, k_big_sort, k_big_rule) beside the lane, binned or
+    generic kernels: bit for bit against the oracle, fault status included."""
+    import acsim
+    cfg, csr = case
+    with acsim.Simulator(cfg, device=0, csr=csr) as g:
+        name = g.kernel_name()
+        g.run()
+        gr, gx, gs = g.rounds(), g.all_values(), g.fault_status()
+        gt = [g.spread_trace(b) for b in range(cfg.n_instances)]
+    # (a handle with a fast path beside its hub rows names them all "k_round_generic(hubs)")
+    assert "k_big_resolve" in name or "+k_round_generic(hubs)" in name, (cfg, name)
+    o = _run_oracle(oracle_mod, cfg, csr)
+    assert np.array_equal(gr, o["rounds"]), cfg
+    assert np.array_equal(gs, o["status"]), cfg
+    assert np.array_equal(_bits(gx), _bits(o["x"])), cfg
+    for b in range(cfg.n_instances):
+        assert np.array_equal(_bits(gt[b]), _bits(o["trace"][b])), (cfg, b)
+
+
+@st.composite
 def binned_configs(draw):
     """One-instance RANDOM_REGULAR configs the binned exchange serves (compiled (d, t) pairs, no
     delays), at sizes that span many source blocks when ACSIM_BIN_SA shrinks them: one-level and

@@ -1,8 +1,12 @@
 """Long randomized GPU-vs-oracle sweep (the strategies of tests/test_properties.py, not
-derandomized): python tools/fuzz_gpu.py [--examples 2000] [--seed S] [--which configs,csr,binned,partitions,resume,steps,hubs,dense,csr_rules]
+derandomized): python tools/fuzz_gpu.py [--examples 2000] [--seed S] [--which configs,csr,binned,partitions,resume,steps,hubs,dense,csr_rules,big_rows]
 
 csr_rules draws tests/test_properties_csr_rules.py's strategy (rules "weighted" and "pushsum" on CSR
 graphs with hub rows, HOLD and link schedules) and checks the handle against the numpy restatement.
+
+big_rows draws tests/test_properties.py's big_row_cases (1 to 4 rows of 8193 .. 140 000 entries on the
+big-m path: every merge-pass count and tail-chunk width of k_big_sort) and checks the handle against
+the oracle.
 
 Prints one line per strategy with the number of passing draws, or the falsifying example.
 """
@@ -53,7 +57,7 @@ def main():
         deg = rng.integers(draw(st.integers(3, 11)), 33, size=n)
         nh = draw(st.integers(1, 6))
         hubs = rng.choice(n, size=nh, replace=False)
-        deg[hubs] = rng.integers(40, 12000, size=nh)
+        deg[hubs] = rng.integers(40, 70000, size=nh)
         rowptr = np.concatenate([[0], np.cumsum(deg)]).astype(np.uint64)
         colidx = rng.integers(0, n, size=int(rowptr[-1])).astype(np.uint32)
         base = draw(T.configs())
@@ -67,6 +71,9 @@ def main():
         return cfg, (rowptr, colidx)
 
     tests["hubs"] = (T.test_gpu_matches_oracle_random_csr, "case", hub_cases())
+
+    # rows above 8192 entries at k_big_sort's pass-count and tail-width boundaries
+    tests["big_rows"] = (T.test_gpu_matches_oracle_random_big_rows, "case", T.big_row_cases())
 
     # complete graphs the persistent dense kernel serves (asserts the kernel; up to 2048 nodes)
     tests["dense"] = (T.test_gpu_dense_random_configs, "cfg", T.dense_configs(max_n=2048))
