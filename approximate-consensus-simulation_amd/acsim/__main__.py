@@ -15,6 +15,9 @@
   python -m acsim run --graph scheduled.npz --set rule=pushsum --set missing_policy=hold
       (a file with a link schedule, graphs.save_csr(..., schedule=...): rules weighted and pushsum run
       on it, reported on stderr; push-sum keeps the mean on a schedule under "hold" only)
+  python -m acsim run --graph scheduled.npz --set rule=pushsum --split
+      (push-sum with per-round splitting on the file's schedule, DESIGN.md §9: no weights, no held
+      state, and the mean is kept; reported on stderr)
 """
 from __future__ import annotations
 
@@ -59,12 +62,20 @@ def _grid(specs):
     return grid
 
 
-def validate(cfg: Config, csr=None, weights=None, schedule=None) -> int:
+def validate(cfg: Config, csr=None, weights=None, schedule=None, split=False) -> int:
     """Host-side §A.8 validation through the library (no GPU needed: acs_create validates first)."""
     lib = _abi.load_library()
     c = cfg.to_c()
     h = C.c_void_p()
-    if csr is not None and weights is not None and schedule is not None:
+    if split:
+        from .graphs import full_schedule
+        rp, ci = csr
+        period, av = schedule if schedule is not None else full_schedule(ci.size, 1)
+        av = np.ascontiguousarray(av, dtype=np.uint32)
+        rc = lib.acs_create_csr_split(C.byref(c), rp.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                      ci.ctypes.data_as(C.POINTER(C.c_uint32)), int(period),
+                                      av.ctypes.data_as(C.POINTER(C.c_uint32)), 0, C.byref(h))
+    elif csr is not None and weights is not None and schedule is not None:
         rp, ci = csr
         ws, we = (np.ascontiguousarray(w, dtype=np.float64) for w in weights)
         av = np.ascontiguousarray(schedule[1], dtype=np.uint32)
@@ -106,6 +117,8 @@ def main(argv=None) -> int:
         p.add_argument("--set", action="append", metavar="FIELD=VALUE")
         p.add_argument("--device", type=int, default=0)
         p.add_argument("--graph", metavar="FILE.npz", help="user CSR graph (acsim.graphs.load_csr)")
+        p.add_argument("--split", action="store_true",
+                       help="rule pushsum with per-round splitting on the graph file's link schedule (no weights)")
         if name in ("run", "sweep"):
             p.add_argument("--out")
         if name == "sweep":
@@ -117,10 +130,25 @@ def main(argv=None) -> int:
         return 0
     cfg = _apply(preset(a.preset), a.set)
     csr = weights = schedule = None
+    if a.split and not a.graph:
+        ap.error("--split needs --graph")
     if a.graph:
         from .config import _enum
         from .graphs import load_csr
-        if _enum("rule", cfg.rule) == _abi.RULE_WEIGHTED:   # the file's weights go with the rule
+        if a.split:   # shares from the schedule: the file's weights are not read
+            if _enum("rule", cfg.rule) != _abi.RULE_PUSHSUM:
+                ap.error("--split needs --set rule=pushsum")
+            csr = load_csr(a.graph)
+            try:
+                schedule = load_csr(a.graph, schedule=True)[2:]
+                print(f"pushsum --split: using the link schedule of {a.graph} (period {schedule[0]}); every sender "
+                      "splits over the links up in each round", file=sys.stderr)
+            except ValueError as e:
+                if "no link schedule" not in str(e):
+                    raise
+                print(f"pushsum --split: {a.graph} has no link schedule, every link is up in every round",
+                      file=sys.stderr)
+        elif _enum("rule", cfg.rule) == _abi.RULE_WEIGHTED:   # the file's weights go with the rule
             g = load_csr(a.graph, weights=True)
             csr, weights = g[:2], g[2:]
         elif _enum("rule", cfg.rule) == _abi.RULE_PUSHSUM:   # the file's weights, else 1 / (outdeg + 1)
@@ -147,21 +175,23 @@ def main(argv=None) -> int:
                     raise
         cfg = cfg.replace(topology="csr", n_nodes=int(csr[0].size - 1))
     if a.cmd == "validate":
-        rc = validate(cfg, csr, weights, schedule)
+        rc = validate(cfg, csr, weights, schedule, split=a.split)
         if rc == 0:
             print("ok")
         return rc
     if a.cmd == "run":
         from .io import save_result
         from .sim import simulate
-        res = simulate(cfg, device=a.device, return_values=bool(a.out), csr=csr, weights=weights, schedule=schedule)
+        res = simulate(cfg, device=a.device, return_values=bool(a.out), csr=csr, weights=weights, schedule=schedule,
+                       split=a.split)
         from .sweep import summarize
         print(json.dumps(summarize(cfg, res)))
         if a.out:
             save_result(a.out, res, cfg)
         return 0
     from .sweep import sweep
-    rows = sweep(cfg, _grid(a.grid), out_dir=a.out, device=a.device, csr=csr, weights=weights, schedule=schedule)
+    rows = sweep(cfg, _grid(a.grid), out_dir=a.out, device=a.device, csr=csr, weights=weights, schedule=schedule,
+                 split=a.split)
     for r in rows:
         print(json.dumps(r))
     return 0

@@ -119,6 +119,8 @@ def _declare(lib: C.CDLL) -> None:
         "acs_create_csr_scheduled": (i32, [P(AcsConfig), P(u64), P(u32), P(C.c_double), P(C.c_double), u32, P(u32),
                                            i32, P(vp)]),
         "acs_get_link_schedule": (i32, [vp, P(u32), P(u32), u64]),
+        "acs_create_csr_split": (i32, [P(AcsConfig), P(u64), P(u32), u32, P(u32), i32, P(vp)]),
+        "acs_get_split_shares": (i32, [vp, P(C.c_double), u64]),
         "acs_comm_id_size": (i32, []),
         "acs_get_comm_id": (i32, [vp, u64]),
         "acs_create_partitioned": (i32, [P(AcsConfig), i32, i32, i32, vp, u64, P(vp)]),

@@ -219,6 +219,37 @@ def pushsum_weights(rowptr, colidx, dtype="f64"):
     return w.copy(), w[ci.astype(np.int64)]
 
 
+def _floor_recip(k, dtype):
+    """1 / k rounded to `dtype`, one ulp lower where k times the rounded value exceeds 1 exactly
+    (decided in integers), for an int64 array k >= 1; float64 values."""
+    ft, p = (np.float32, 24) if str(dtype) in ("f32", "float32") else (np.float64, 53)
+    uk, inv = np.unique(np.asarray(k, dtype=np.int64), return_inverse=True)
+    w = (ft(1) / uk.astype(ft)).astype(ft)
+    m, e = np.frexp(w.astype(np.float64))   # w = mi * 2^(e - p) with mi = the p-bit significand
+    mi = np.ldexp(m, p).astype(np.int64)
+    for q in range(uk.size):
+        while int(mi[q]) * int(uk[q]) > 1 << int(p - e[q]):
+            w[q] = np.nextafter(w[q], ft(0))
+            m1, e1 = np.frexp(np.float64(w[q]))
+            mi[q], e[q] = int(np.ldexp(m1, p)), e1
+    return w.astype(np.float64)[inv].reshape(np.shape(k))
+
+
+def split_shares(rowptr, colidx, period, avail, dtype="f64"):
+    """The share table of push-sum with per-round splitting (Simulator(..., split=True)):
+    share[p, j] = 1 / c_p(j) with c_p(j) = 1 + the slots of sender j that are up in phase p, rounded
+    to `dtype` and taken one ulp lower where c_p(j) times the rounded share exceeds 1 exactly (the
+    rule of pushsum_weights), so every round's column sums are at most 1.  Returns float64 [period, N]."""
+    rp, ci = check_csr(rowptr, colidx)
+    period, av = check_schedule(rp, period, avail)
+    n = rp.size - 1
+    c = np.ones((period, n), dtype=np.int64)
+    for p in range(period):
+        up = (av >> np.uint32(p)) & np.uint32(1)
+        c[p] += np.bincount(ci.astype(np.int64), weights=up, minlength=n).astype(np.int64)
+    return _floor_recip(c, dtype)
+
+
 def column_sums(rowptr, colidx, w_self, w_edge):
     """Column sums of the weight matrix: w_self[j] plus every w_edge[slot] with colidx[slot] == j,
     each as a correctly rounded sum (math.fsum).  Rule "pushsum" needs every one <= 1 + 2^-30."""

@@ -45,7 +45,7 @@ class Simulator:
 
     def __init__(self, cfg: Config | str, device: int = 0, backend: str = "hip",
                  partitions: int = 1, rank: int = 0, comm_id: Optional[bytes] = None,
-                 csr=None, weights=None, schedule=None):
+                 csr=None, weights=None, schedule=None, split=False):
         """partitions > 1 node-partitions one RANDOM_REGULAR instance: with
         comm_id (RCCL unique id from acsim.distributed) this handle is `rank`'s partition on
         `device`; without it all partitions are simulated on `device` with private x copies
@@ -58,7 +58,12 @@ class Simulator:
         schedule = (period, avail[nnz]) with csr and weights ("Link schedules"): bit p of
         avail[s] is set when the link on slot s is up in every round r with r % period == p; a message on
         a slot that is down is missing exactly as a dropped one.  Push-sum keeps the mean on a schedule
-        only with missing_policy="hold" ("omit" loses the mass of every down link)."""
+        only with missing_policy="hold" ("omit" loses the mass of every down link).
+
+        split=True with csr and rule="pushsum", and no weights ("Push-sum with per-round
+        splitting"): in every round a sender divides its pair over itself and its links that are up
+        in that round, so the mean is kept on any schedule with no held state.  Without a schedule
+        every link is up in every round (graphs.full_schedule(nnz, 1))."""
         if isinstance(cfg, str):
             cfg = preset(cfg)
         if backend != "hip":
@@ -71,9 +76,26 @@ class Simulator:
         h = C.c_void_p()
         if weights is not None and csr is None:
             raise ValueError("weights need a csr graph")
-        if schedule is not None and (csr is None or weights is None):
+        if split and weights is not None:
+            raise ValueError("split=True computes the shares from the schedule: it takes no weights")
+        if split and csr is None:
+            raise ValueError("split=True needs a csr graph")
+        if schedule is not None and (csr is None or (weights is None and not split)):
             raise ValueError("a link schedule needs a csr graph with weights (rule 'weighted' or 'pushsum')")
-        if csr is not None and weights is not None:   # rule="weighted" / "pushsum" (acs_create_csr_weighted)
+        if split:   # rule="pushsum" with per-round splitting (acs_create_csr_split)
+            from .graphs import check_schedule, full_schedule
+            rp = np.ascontiguousarray(csr[0], dtype=np.uint64)
+            ci = np.ascontiguousarray(csr[1], dtype=np.uint32)
+            if rp.size != int(cfg.n_nodes) + 1:
+                raise ValueError("rowptr must have n_nodes + 1 entries")
+            self._nnz = int(ci.size)
+            period, av = check_schedule(rp, *(schedule if schedule is not None else full_schedule(ci.size, 1)),
+                                        values=False)
+            self._period = period
+            rc = self._lib.acs_create_csr_split(
+                C.byref(self._c), rp.ctypes.data_as(C.POINTER(C.c_uint64)), ci.ctypes.data_as(C.POINTER(C.c_uint32)),
+                period, av.ctypes.data_as(C.POINTER(C.c_uint32)), int(device), C.byref(h))
+        elif csr is not None and weights is not None:   # rule="weighted" / "pushsum" (acs_create_csr_weighted)
             rp = np.ascontiguousarray(csr[0], dtype=np.uint64)
             ci = np.ascontiguousarray(csr[1], dtype=np.uint32)
             ws = np.ascontiguousarray(weights[0], dtype=np.float64)
@@ -298,6 +320,14 @@ class Simulator:
                                                   av.size))
         return int(period.value), av
 
+    def split_shares(self) -> np.ndarray:
+        """[period, N] shares of a handle made with split=True as the device holds them (dtype="f32":
+        widened to float64): share[p, j] is what node j keeps, and sends on each link that is up, in
+        the rounds r with r % period == p."""
+        out = np.empty((getattr(self, "_period", 1), self.N), dtype=np.float64)
+        self._chk(self._lib.acs_get_split_shares(self._h, out.ctypes.data_as(C.POINTER(C.c_double)), out.size))
+        return out
+
     def neighbors(self) -> np.ndarray:
         d = int(self.cfg.degree)
         out = np.empty(self.N * d, dtype=np.uint32)
@@ -328,7 +358,7 @@ class Simulator:
 
 def simulate(cfg: Config | str, backend: str = "hip", device: int = 0,
              devices: Optional[Sequence[int]] = None, return_values: bool = True,
-             csr=None, weights=None, schedule=None) -> Result:
+             csr=None, weights=None, schedule=None, split=False) -> Result:
     """Run one configuration to termination and return its results."""
     if devices is not None:
         devices = list(devices)
@@ -336,7 +366,8 @@ def simulate(cfg: Config | str, backend: str = "hip", device: int = 0,
             raise ValueError("simulate() drives one device per process; shard instances across "
                              "processes with acsim.distributed (one rank per GPU)")
         device = devices[0]
-    with Simulator(cfg, device=device, backend=backend, csr=csr, weights=weights, schedule=schedule) as sim:
+    with Simulator(cfg, device=device, backend=backend, csr=csr, weights=weights, schedule=schedule,
+                   split=split) as sim:
         res = sim.run()
         x = None
         if return_values:

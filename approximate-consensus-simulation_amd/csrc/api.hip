@@ -102,6 +102,40 @@ int acs_create_csr_scheduled(const acs_config* cfg, const uint64_t* rowptr, cons
     return validate_and_create(cfg, device, 1, 0, nullptr, 0, out, rowptr, colidx, w_self, w_edge, &sched);
 }
 
+int acs_create_csr_split(const acs_config* cfg, const uint64_t* rowptr, const uint32_t* colidx, uint32_t period,
+                         const uint32_t* avail, int device, acs_sim** out) {
+    if (out) *out = nullptr;
+    if (!cfg || cfg->topology != ACS_TOPO_CSR) return fail(ACS_EINVAL, "config topology must be ACS_TOPO_CSR");
+    if (cfg->rule != ACS_RULE_PUSHSUM)
+        return fail(ACS_EINVAL, "acs_create_csr_split takes rule ACS_RULE_PUSHSUM only (got rule %u)", cfg->rule);
+    if (!rowptr || !colidx) return fail(ACS_EINVAL, "null CSR arrays");
+    if (!out) return fail(ACS_EINVAL, "null out");
+    if (int rc = validate(cfg)) return rc;   // (before the HOLD check: an invalid config is ACS_EINVAL first)
+    if (cfg->missing_policy == ACS_MISSING_HOLD)
+        return fail(ACS_EUNSUPPORTED, "push-sum with per-round splitting does not serve missing_policy = HOLD: a lost "
+                                      "message's mass is lost, as under OMIT");
+    LinkSchedule sched{period, avail};   // (checked with the arrays: sched_check.hpp)
+    sched.split = true;
+    return create_impl(cfg, device, 1, 0, nullptr, 0, out, rowptr, colidx, nullptr, nullptr, &sched);
+}
+
+int acs_get_split_shares(acs_sim* s, double* out, uint64_t n) {
+    if (!s || !out) return fail(ACS_EINVAL, "null argument");
+    if (!s->split) return fail(ACS_EINVAL, "acs_get_split_shares: not a handle of acs_create_csr_split");
+    if (n != (uint64_t)s->period * s->N)
+        return fail(ACS_EINVAL, "acs_get_split_shares: expected n = period * N = %llu", (unsigned long long)(s->period * s->N));
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (s->f32) {
+        std::vector<float> f(n);
+        HIP_TRY(hipMemcpy(f.data(), s->share, n * sizeof(float), hipMemcpyDeviceToHost));
+        for (uint64_t k = 0; k < n; ++k) out[k] = f[k];
+    } else {
+        HIP_TRY(hipMemcpy(out, s->share, n * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return ACS_OK;
+}
+
 int acs_get_link_schedule(acs_sim* s, uint32_t* period_out, uint32_t* avail_out, uint64_t nnz) {
     if (!s || !period_out || (!avail_out && nnz)) return fail(ACS_EINVAL, "null argument");
     if (!s->sched) return fail(ACS_EINVAL, "acs_get_link_schedule: not a handle of acs_create_csr_scheduled");
@@ -121,6 +155,20 @@ int acs_get_weights(acs_sim* s, double* w_self_out, uint64_t n, double* w_edge_o
                     (unsigned long long)s->nnz);
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(s->stream));
+    if (s->split) {   // phase 0's effective weights: the sender's share on an up slot, +0.0 on a down one
+        std::vector<uint32_t> ci(nnz), av(nnz);
+        if (s->f32) {
+            std::vector<float> f(n);
+            HIP_TRY(hipMemcpy(f.data(), s->share, n * sizeof(float), hipMemcpyDeviceToHost));
+            for (uint64_t k = 0; k < n; ++k) w_self_out[k] = f[k];
+        } else {
+            HIP_TRY(hipMemcpy(w_self_out, s->share, n * sizeof(double), hipMemcpyDeviceToHost));
+        }
+        if (nnz) HIP_TRY(hipMemcpy(ci.data(), s->colidx, nnz * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (nnz) HIP_TRY(hipMemcpy(av.data(), s->avail, nnz * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (uint64_t e = 0; e < nnz; ++e) w_edge_out[e] = (av[e] & 1u) ? w_self_out[ci[e]] : 0.0;
+        return ACS_OK;
+    }
     if (s->f32) {
         std::vector<float> fs(n), fe(nnz);
         HIP_TRY(hipMemcpy(fs.data(), s->wself, n * sizeof(float), hipMemcpyDeviceToHost));
@@ -357,6 +405,9 @@ int acs_set_state(acs_sim* s, uint32_t round, const void* x, uint64_t n) {
     }
     if (s->pushsum)   // s = x, z = 1
         HIP_TRY(launch_pushsum_fill(xb(s, round), pairs_at(s, round), s->B * s->N, s->f32, s->stream));
+    if (s->split)     // the offers of round `round`: its phase's shares of the new pairs
+        HIP_TRY(launch_pushsum_offer(pairs_at(s, round), share_at(s, round), offers_at(s, round), s->B, s->N, s->f32,
+                                     s->stream));
     if (s->hold)      // and every link empty (a resume with held mass calls acs_set_pushsum_links next)
         HIP_TRY(hipMemsetAsync(s->links, 0, links_bytes(s), s->stream));
     return init_state(s, round);
@@ -423,6 +474,9 @@ int acs_set_pushsum_state(acs_sim* s, uint32_t round, const void* sv, const void
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipMemcpyAsync(pairs_at(s, round), h.data(), h.size(), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(launch_pushsum_estimate(pairs_at(s, round), xb(s, round), n, s->f32, s->stream));
+    if (s->split)   // as acs_set_state: the offers are rebuilt with the shares of phase round mod period
+        HIP_TRY(launch_pushsum_offer(pairs_at(s, round), share_at(s, round), offers_at(s, round), s->B, s->N, s->f32,
+                                     s->stream));
     if (s->hold) HIP_TRY(hipMemsetAsync(s->links, 0, links_bytes(s), s->stream));   // as acs_set_state
     return init_state(s, round);   // (synchronises: h outlives the copy)
 }

@@ -5,6 +5,7 @@
 #include "csr_lane.hpp"
 #include "handle.hpp"
 #include "sched_check.hpp"
+#include "split_shares.hpp"
 
 using namespace acs;
 
@@ -219,6 +220,8 @@ void release(acs_sim* s) {
     (void)hipFree(s->links);
     (void)hipFree(s->avail);
     (void)hipFree(s->avell);
+    (void)hipFree(s->share);
+    (void)hipFree(s->offers);
     (void)hipFree(s->gen_ids);
     (void)hipFree(s->crank);
     (void)hipFree(s->clist);
@@ -544,7 +547,7 @@ static int build_csr(acs_sim* s, const CreateOptions& o, const CsrCheck& chk, co
     STAGE_TRY(hipMalloc(&s->colidx, (nnz ? nnz : 1) * sizeof(uint32_t)));
     STAGE_TRY(hipMemcpy(s->rowptr, h_rowptr, (s->N + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
     if (nnz) STAGE_TRY(hipMemcpy(s->colidx, h_colidx, nnz * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (s->weighted) {
+    if (s->weighted && !s->split) {
         STAGE_TRY(hipMalloc(&s->wself, s->N * s->es));
         STAGE_TRY(hipMalloc(&s->wedge, (nnz ? nnz : 1) * s->es));
         if (s->f32) {   // (exact: the values were rounded to binary32 by the check)
@@ -560,6 +563,17 @@ static int build_csr(acs_sim* s, const CreateOptions& o, const CsrCheck& chk, co
         STAGE_TRY(hipMalloc(&s->avail, (nnz ? nnz : 1) * sizeof(uint32_t)));
         if (nnz) STAGE_TRY(hipMemcpy(s->avail, h_sched->avail, nnz * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
+    if (s->split) {   // the share table [period][N], in the config dtype (exact: the values were rounded to it)
+        std::vector<double> sh;
+        split_shares(sh, s->f32, s->N, nnz, h_colidx, s->period, h_sched->avail);
+        STAGE_TRY(hipMalloc(&s->share, sh.size() * s->es));
+        if (s->f32) {
+            std::vector<float> fs(sh.begin(), sh.end());
+            STAGE_TRY(hipMemcpy(s->share, fs.data(), fs.size() * sizeof(float), hipMemcpyHostToDevice));
+        } else {
+            STAGE_TRY(hipMemcpy(s->share, sh.data(), sh.size() * sizeof(double), hipMemcpyHostToDevice));
+        }
+    }
     if (!s->csr_var) return ACS_OK;
     const uint64_t words = ((s->N + 63) / 64) * 64ull * s->dp;
     STAGE_TRY(hipMalloc(&s->ell, words * sizeof(uint32_t)));
@@ -568,7 +582,7 @@ static int build_csr(acs_sim* s, const CreateOptions& o, const CsrCheck& chk, co
     STAGE_TRY(hipMemsetAsync(s->ell, 0xFF, words * sizeof(uint32_t), s->stream));
     STAGE_TRY(launch_csr_to_ell(s->rowptr, s->colidx, s->N, s->d, s->ell, s->deg, s->sw, s->stream));
     if (s->ell_sorted) STAGE_TRY(launch_sort_ell_rows(s->ell, s->N, s->d, s->stream));
-    if (s->weighted) {
+    if (s->weighted && !s->split) {
         STAGE_TRY(hipMalloc(&s->well, words * s->es));
         STAGE_TRY(launch_weights_to_ell(s->rowptr, s->wedge, s->deg, s->N, s->d, s->f32, s->well, s->stream));
     }
@@ -668,7 +682,8 @@ static std::string kernel_name_of(const acs_sim* s) {
     } else if (s->csr_var) {
         const std::string w = "<" + std::to_string(s->d) + (s->sched ? ",csr,sched>" : ",csr>");   // (SCHED instantiations)
         // (k_round_pushsum_hold: the reported name of k_round_pushsum's HOLD = true instantiation)
-        nm = s->hold     ? "k_round_pushsum_hold" + w
+        nm = s->split    ? "k_round_pushsum_split<" + std::to_string(s->d) + ",csr>"
+           : s->hold     ? "k_round_pushsum_hold" + w
            : s->pushsum  ? "k_round_pushsum" + w
            : s->weighted ? "k_round_weighted" + w
                          : "k_round_regular<" + std::to_string(s->d) + "," + std::to_string(c.trim) + ",csr>";
@@ -694,6 +709,10 @@ static int finish_handle(acs_sim* s, const CreateOptions& o, const void* comm_id
     if (s->pushsum) {   // round 0: s = x^0, z = 1 (Npad == N: CSR handles are not partitioned)
         STAGE_TRY(hipMalloc(&s->pairs, 2 * s->B * s->N * 2 * s->es));
         STAGE_TRY(launch_pushsum_fill(s->x[0], pairs_at(s, 0), s->B * s->N, s->f32, s->stream));
+    }
+    if (s->split) {   // round 0's offers: phase 0's shares of (x^0, 1)
+        STAGE_TRY(hipMalloc(&s->offers, 2 * s->B * s->N * 2 * s->es));
+        STAGE_TRY(launch_pushsum_offer(pairs_at(s, 0), share_at(s, 0), offers_at(s, 0), s->B, s->N, s->f32, s->stream));
     }
     if (s->hold) {   // every link starts empty: (+0.0, +0.0)
         STAGE_TRY(hipMalloc(&s->links, links_bytes(s)));
@@ -744,12 +763,17 @@ static int check_arguments(const acs_config* cfg, int device, int nranks, int ra
         if (nranks != 1) return fail(ACS_EUNSUPPORTED, "node partitioning needs RANDOM_REGULAR");
         if (csr_check_arrays(chk, *cfg, h_rowptr, h_colidx)) return fail(chk.code, "%s", chk.message.c_str());
     }
-    if (cfg->rule == ACS_RULE_WEIGHTED || cfg->rule == ACS_RULE_PUSHSUM) {
+    const bool split = h_sched && h_sched->split;
+    if (split) {   // (no weights: the shares follow from the schedule; the generic kernel's row limit stays)
+        if (chk.mmax > kGenericMaxM)
+            return fail(ACS_EUNSUPPORTED, "rule PUSHSUM serves rows of at most %u entries (largest row: %llu)", kGenericMaxM,
+                        (unsigned long long)chk.mmax);
+    } else if (cfg->rule == ACS_RULE_WEIGHTED || cfg->rule == ACS_RULE_PUSHSUM) {
         if (!h_wself || !h_wedge) return fail(ACS_EINVAL, "rule WEIGHTED needs acs_create_csr_weighted(w_self, w_edge)");
         if (csr_check_weights(chk, *cfg, h_rowptr, h_colidx, h_wself, h_wedge))
             return fail(chk.code, "%s", chk.message.c_str());
     }
-    if (h_sched && sched_check(chk, *cfg, chk.nnz, h_sched->period, h_sched->avail))
+    if (h_sched && sched_check(chk, *cfg, chk.nnz, h_sched->period, h_sched->avail, split))
         return fail(chk.code, "%s", chk.message.c_str());
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail(ACS_EINVAL, "bad rank / n_ranks");
     const bool partitioned = nranks > 1 || comm_id != nullptr;
@@ -793,6 +817,7 @@ static acs_sim* new_handle(const acs_config& c, int device, int nranks, int rank
     s->nnz = chk.nnz;
     s->sched = h_sched != nullptr;
     s->period = h_sched ? h_sched->period : 0;
+    s->split = h_sched && h_sched->split;
     // "clean": no slot-dependent decision at all (no faults, no loss, no delays, no link schedule)
     s->clean = c.fault_model == ACS_FAULT_NONE && drop_threshold(c.loss_p) == 0 && c.delay_max == 0 && !s->sched;
     s->mp.key = key_of(c.seed);

@@ -13,6 +13,9 @@
 //               dtype (double2 / float2); instance b at round r lives in pairs[r & 1], beside x
 //   links     : rule PUSHSUM with missing_policy = HOLD only: one buffer [B][nnz] of
 //               held (h, k) pairs in CSR slot order, updated in place by each slot's receiver
+//   share, offers : rule PUSHSUM with per-round splitting only: the share table
+//               [period][N] of the config dtype, and two buffers [B][N] of offers (share * pair) by
+//               round parity, beside pairs; such a handle has no wself / wedge / well and no links
 //   status    : u32 [B][N] fault status (§A.4), absent when there are no faults
 //   st        : InstState [B] — honest lo/hi/spread of the current round, rounds, done flags
 //   partial   : double2 [B][nblk] per-block honest (min, max) partials of x^{r+1} (§A.8)
@@ -112,6 +115,13 @@ struct RoundArgs {
     const uint32_t* avail;
     const uint32_t* avell;
     uint32_t phase;
+    // rule PUSHSUM with per-round splitting (handles of acs_create_csr_split): every
+    // node's offer share_p(j) * (s_j, z_j) + 0.0 of round r (oin) and of round r + 1 (oout, which the
+    // round writes), instance-major [B][N] of double2 (fp32: float2), and share_next[i] = node i's
+    // share in phase (r + 1) mod period.  nullptr for every other handle.
+    const void* oin;
+    void* oout;
+    const void* share_next;
 };
 constexpr uint32_t kEaccSlots = 32, kEaccStride = 16;       // eacc pairs, u64 words between pairs
 constexpr uint32_t kEaccWords = kEaccSlots * kEaccStride;   // eacc words of one round parity
@@ -228,6 +238,16 @@ hipError_t launch_round_pushsum(const RoundArgs& a, bool hold, uint64_t B, uint3
 hipError_t launch_pushsum_fill(const void* x, void* pairs, uint64_t n, bool f32, hipStream_t s);
 // x[k] = s / z where z > 0, else s (acs_set_pushsum_state)
 hipError_t launch_pushsum_estimate(const void* pairs, void* x, uint64_t n, bool f32, hipStream_t s);
+
+// Rule PUSHSUM with per-round splitting (round_pushsum_split.hip): one lane per receiver over the
+// padded ELL and the masks in its order (a.avell); a lane gathers its senders' offers (a.oin) and
+// also stores its own next offer (a.oout).  No weights, no links.  Hub rows are skipped
+// (k_round_generic's split sub-branch of rule 6).
+hipError_t launch_round_pushsum_split(const RoundArgs& a, uint64_t B, uint32_t nblk_fast, hipStream_t s);
+// offers[b][i] = share[i] * pairs[b][i] + 0.0 for B instances of N nodes (create, acs_set_state,
+// acs_set_pushsum_state); share: the N shares of the phase the next round runs in
+hipError_t launch_pushsum_offer(const void* pairs, const void* share, void* offers, uint64_t B, uint64_t N, bool f32,
+                                hipStream_t s);
 
 // Binned exchange (round_binned.hip): the one-instance RANDOM_REGULAR round as streaming kernels
 // instead of N·d random 8-byte gathers (clean, lossy and faulty configs; no delays).  Deliveries (i <- j) are grouped into

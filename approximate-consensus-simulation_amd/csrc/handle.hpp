@@ -168,6 +168,13 @@ struct acs_sim {
     uint32_t period = 0;
     uint32_t* avail = nullptr;     // [nnz]
     uint32_t* avell = nullptr;     // (csr_var; RoundArgs::avell)
+    // rule PUSHSUM with per-round splitting (handles of acs_create_csr_split, which are
+    // scheduled handles with no weights: wself, wedge, well and links stay null): the share table
+    // [period][N] of the config dtype, and every node's offer beside its pair, two buffers [B][N] of
+    // pairs by round parity
+    bool split = false;
+    void* share = nullptr;
+    void* offers = nullptr;
     double* dsorted = nullptr;     // dense path: sorted base multiset [N]
     uint32_t* dcounts = nullptr;   // dense path: |B|, #Byzantine, #crash-silent
     std::vector<Part> parts;       // virtual partitions 1..P-1 (partition 0 uses x / ell)
@@ -217,6 +224,13 @@ static inline void* xat(const acs_sim* s, const void* base, uint64_t k) {
 static inline void* pairs_at(const acs_sim* s, uint32_t q) {
     return static_cast<char*>(s->pairs) + (uint64_t)(q & 1u) * s->B * s->N * 2 * s->es;
 }
+// ... with per-round splitting: the offer buffer of round q, and the shares of the phase round q runs in
+static inline void* offers_at(const acs_sim* s, uint32_t q) {
+    return static_cast<char*>(s->offers) + (uint64_t)(q & 1u) * s->B * s->N * 2 * s->es;
+}
+static inline void* share_at(const acs_sim* s, uint32_t q) {
+    return static_cast<char*>(s->share) + (uint64_t)(q % s->period) * s->N * s->es;
+}
 // rule PUSHSUM under HOLD: bytes of the link buffer (at least one pair, so the pointer is never null)
 static inline uint64_t links_bytes(const acs_sim* s) { return (s->B * s->nnz ? s->B * s->nnz : 1) * 2 * s->es; }
 static inline uint64_t part_row0(const acs_sim* s, int p) { return (uint64_t)p * s->rows_per; }
@@ -230,6 +244,7 @@ static inline uint64_t part_rows(const acs_sim* s, int p) {
 struct LinkSchedule {   // acs_create_csr_scheduled's arguments as given (sched_check.hpp checks them)
     uint32_t period;
     const uint32_t* avail;
+    bool split = false;   // acs_create_csr_split: no weights, shares from the schedule (split_shares.hpp)
 };
 int validate(const acs_config* c);   // §A.8 constraints
 // A handle for a validated config (the callers in api.hip validate); *out is null on any failure.

@@ -216,12 +216,22 @@ __global__ __launch_bounds__(BLK) void k_round_generic(const RoundArgs a, uint32
         // (hn = h_e + a, kn = k_e + c); a delivered message contributes (hn, kn) and empties the link,
         // a dropped one contributes +0.0 and leaves (hn, kn) on it.  In place: one thread per slot.
         V2* lk = a.lnk ? reinterpret_cast<V2*>(a.lnk) + (uint64_t)lb * a.lnk_stride : nullptr;
+        // per-round splitting (a.oin; k_round_pushsum_split): an entry is its sender's offer as stored
+        // (entry 0: the row's own), +0.0 on a slot that is down or dropped; the row's next offer is
+        // stored with its pair.
+        const V2* __restrict__ oin = a.oin ? reinterpret_cast<const V2*>(a.oin) + lb * N : nullptr;
         for (uint32_t e = threadIdx.x; e < P; e += BLK) {
             VT pe = VT(0), ze = VT(0);
             if (e < m) {
                 const uint64_t slot = rp + e - 1;   // (entry 0 has no slot)
                 const bool dropped = e != 0 && slot_missing(a, mp, bG, a.r, slot);
-                if (lk && e != 0) {
+                if (oin) {
+                    if (!dropped) {
+                        const V2 v = oin[e == 0 ? i : a.colidx[slot]];
+                        pe = v.x;
+                        ze = v.y;
+                    }
+                } else if (lk && e != 0) {
                     const VT wt = we[slot];
                     const V2 v = pin[a.colidx[slot]];
                     const V2 l = lk[slot];
@@ -252,6 +262,13 @@ __global__ __launch_bounds__(BLK) void k_round_generic(const RoundArgs a, uint32
             o.x = num;
             o.y = den;
             (reinterpret_cast<V2*>(a.pout) + lb * N)[i] = o;
+            if (oin) {
+                const VT shn = reinterpret_cast<const VT*>(a.share_next)[i];
+                V2 nx;
+                nx.x = shn * num + VT(0);
+                nx.y = shn * den + VT(0);
+                (reinterpret_cast<V2*>(a.oout) + lb * N)[i] = nx;
+            }
             xo[i] = res;
             *part = make_double2((double)res, (double)res);
         }

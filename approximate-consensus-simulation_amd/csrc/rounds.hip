@@ -164,6 +164,11 @@ static RoundArgs round_args(acs_sim* s, uint32_t r) {
         a.lnk = s->links;   // (HOLD handles only: null selects the plain rule in k_round_generic)
         a.lnk_stride = s->nnz;
     }
+    if (s->split) {   // (this round's shares are in the offers already)
+        a.oin = offers_at(s, r);
+        a.oout = offers_at(s, r + 1);
+        a.share_next = share_at(s, r + 1);
+    }
     return a;
 }
 
@@ -327,6 +332,8 @@ static int enqueue_round(acs_sim* s, uint32_t r) {
             if (s->n_hub) ab.qhi = s->nblk_fast;   // the hub rows' partial slots are the generic kernel's
             HIP_TRY(launch_round_binned(s->bin, ab, s->clean, s->stream, s->fin_pending ? &s->fin_args : nullptr));
             s->fin_pending = false;
+        } else if (s->path == PATH_REGULAR && s->split) {
+            HIP_TRY(launch_round_pushsum_split(a, s->B, s->nblk_fast, s->stream));
         } else if (s->path == PATH_REGULAR && s->pushsum) {
             HIP_TRY(launch_round_pushsum(a, s->hold, s->B, s->nblk_fast, s->stream));
         } else if (s->path == PATH_REGULAR && s->weighted) {

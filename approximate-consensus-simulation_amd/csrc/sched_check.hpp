@@ -18,7 +18,10 @@ inline uint32_t sched_full_mask(uint32_t period) { return period >= 32 ? 0xFFFFF
 // is allowed.  Served for rules WEIGHTED and PUSHSUM.  PUSHSUM with missing_policy = SELF needs
 // every slot up in every phase, for the reason loss needs OMIT or HOLD: SELF would put the
 // receiver's own pair in place of the missing message and create mass.
-inline int sched_check(CsrCheck& r, const acs_config& c, uint64_t nnz, uint32_t period, const uint32_t* avail) {
+// split (acs_create_csr_split, "Push-sum with per-round splitting"): senders pay nothing out on a
+// down link, so nothing is missing there and SELF takes any mask.
+inline int sched_check(CsrCheck& r, const acs_config& c, uint64_t nnz, uint32_t period, const uint32_t* avail,
+                       bool split = false) {
     if (c.rule != ACS_RULE_WEIGHTED && c.rule != ACS_RULE_PUSHSUM)
         return r.fail(ACS_EUNSUPPORTED, "link schedules are served for rules WEIGHTED and PUSHSUM (got rule %u)", c.rule);
     if (period < 1 || period > ACS_SCHEDULE_MAX_PERIOD)
@@ -29,7 +32,7 @@ inline int sched_check(CsrCheck& r, const acs_config& c, uint64_t nnz, uint32_t 
         if (avail[e] & ~full)
             return r.fail(ACS_EINVAL, "link schedule: avail[%llu] = 0x%08x has a bit at a position >= period %u",
                           (unsigned long long)e, avail[e], period);
-    if (c.rule == ACS_RULE_PUSHSUM && c.missing_policy == ACS_MISSING_SELF)
+    if (c.rule == ACS_RULE_PUSHSUM && c.missing_policy == ACS_MISSING_SELF && !split)
         for (uint64_t e = 0; e < nnz; ++e)
             if (avail[e] != full)
                 return r.fail(ACS_EINVAL, "link schedule: PUSHSUM with a slot that is down in some phase (avail[%llu] = 0x%08x, "

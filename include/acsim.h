@@ -32,7 +32,8 @@ extern "C" {
                                   additions; acs_config and every older symbol are unchanged;
                                   likewise ACS_MISSING_HOLD and acs_get / acs_set_pushsum_links;
                                   likewise ACS_SCHEDULE_MAX_PERIOD, acs_create_csr_scheduled and
-                                  acs_get_link_schedule) */
+                                  acs_get_link_schedule; likewise acs_create_csr_split and
+                                  acs_get_split_shares) */
 
 /* status codes */
 #define ACS_OK            0
@@ -231,6 +232,24 @@ int acs_create_csr_scheduled(const acs_config* cfg, const uint64_t* rowptr, cons
                              uint32_t period, const uint32_t* avail, int device, struct acs_sim** out);
 /* period into *period_out, nnz masks in slot order into avail_out; ACS_EINVAL on an unscheduled handle */
 int acs_get_link_schedule(struct acs_sim* sim, uint32_t* period_out, uint32_t* avail_out, uint64_t nnz);
+
+/* DESIGN.md §9 ("Push-sum with per-round splitting"): rule PUSHSUM on a link schedule with no weights.
+ * In round r, phase p = r mod P, sender j divides its pair by c_p(j) = 1 + (its slots that are up in
+ * phase p): share_p(j) = 1 / c_p(j) rounded to the config dtype, one ulp lower where c_p(j) * share
+ * would exceed 1 exactly.  Every round's matrix is column-stochastic, so the mean is kept on any
+ * schedule with no per-link state; a message lost to loss_p loses its mass, as under OMIT.
+ * The schedule is acs_create_csr_scheduled's and is checked the same way, except that slots that are
+ * down in some phase are allowed under missing_policy = SELF when loss_p == 0 (nothing is sent on a
+ * down link, so nothing is missing).  Checked on the host before any device call: a rule other than
+ * PUSHSUM, trim != 0, a fault model, loss_p > 0 with SELF (ACS_EINVAL); missing_policy = HOLD,
+ * delay_max > 0, a row above 8192 entries (ACS_EUNSUPPORTED).
+ * acs_get_link_schedule, acs_get / acs_set_pushsum_state and acs_set_state serve the handle;
+ * acs_get_weights returns phase 0's effective weights (0 on a slot that is down in phase 0). */
+int acs_create_csr_split(const acs_config* cfg, const uint64_t* rowptr, const uint32_t* colidx,
+                         uint32_t period, const uint32_t* avail, int device, struct acs_sim** out);
+/* The share table as the device holds it, phase-major: out[p * N + j] = share_p(j), n = P * N values
+ * (fp32 handles: widened to double).  ACS_EINVAL on any handle not made by acs_create_csr_split. */
+int acs_get_split_shares(struct acs_sim* sim, double* out, uint64_t n);
 
 /* §8(e) node partitioning of ONE RANDOM_REGULAR instance over n_ranks GPUs (cfg5), one process
  * (or thread) per GPU.  Rank r owns the 64-aligned row block [r*R, (r+1)*R) ∩ [0, N),
