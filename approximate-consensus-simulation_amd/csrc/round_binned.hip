@@ -395,8 +395,8 @@ __global__ __launch_bounds__(SB, FAULTY && NP > 1 ? ACS_FAULTY_WPE_OF(T, WMSR) :
         if (clampm && !nar && !uni && threadIdx.x < 16 / sizeof(VT)) raw[cap + threadIdx.x] = VT(0);   // +0 bits
     }
     // ordinary loads next (their wait is the barrier's vmcnt(0) anyway)
-    // (x_i is loaded in uniform rounds too, where it is the header's value: skipping the load in the
-    // prefetched kernels measured 2-3 us slower there and about 1.5 us in the 4-byte rounds)
+    // (x_i is the header's value in a uniform round and unused there since the rule runs once per
+    // workgroup; with the rule in every lane, skipping the load had measured slower: DESIGN.md §5.15)
     const VT xi = live ? reinterpret_cast<const VT*>(a.xin)[i] : VT(0);
     uint32_t si = kHonest;
     if constexpr (FLT) {
@@ -480,12 +480,14 @@ __global__ __launch_bounds__(SB, FAULTY && NP > 1 ? ACS_FAULTY_WPE_OF(T, WMSR) :
         }
     }
     VT v[D + 1];
+    VT x0 = xi;   // the receiver's own input to the rule
     bool picked = false;
     if constexpr (NAR) {
         if (uni) {   // uniform round: every delivered value is the header's bit pattern (and so is x_i)
             const VT u = __longlong_as_double((long long)((uint64_t)nh.x | (uint64_t)nh.y << 32));
 #pragma unroll
             for (int t = 0; t < D; ++t) v[1 + t] = u;
+            x0 = u;   // (x_i is not used in a uniform round: the compiler may drop its load on this path)
             if (a.ts) t1 = __builtin_amdgcn_s_memrealtime();
             picked = true;
         } else if (nar) {   // narrow round: the block's u32 image in one pass, values = base + offset
@@ -670,6 +672,45 @@ __global__ __launch_bounds__(SB, FAULTY && NP > 1 ? ACS_FAULTY_WPE_OF(T, WMSR) :
     }
 
     double mn = kInf, mx = -kInf;
+    if constexpr (NAR) {
+        // Narrow plans' tail (clean fp64: every lane honest and active).  In a uniform round the D + 1
+        // inputs are the same for every receiver, so the rule's value is one number: wave 0 evaluates
+        // it (every lane of it, live or not: the inputs do not depend on the lane) through the same
+        // call site as the other rounds, and the workgroup takes it from LDS.  VALU time is paid per
+        // wave, and 2^20 lanes evaluating it cost 16 384 evaluations of one value.
+        VT res = VT(0);
+        if (uni ? w == 0 : live) {
+            v[0] = x0;
+#if ACS_DIAG_B == 1
+            if (NP == 2)
+                res = tree_sum_const<D + 1>(v) / (VT)(D + 1);
+            else
+#endif
+            res = apply_rule_reg<D, T, WMSR, true>(a.rule, v);
+        }
+        if (uni) {
+            // (raw holds nothing in a uniform round: no part, no image and no zero slot was written.
+            // The barrier is outside `live`: the dead waves of a ragged last block reach it too.)
+            if (threadIdx.x == 0) raw[0] = res;
+            __syncthreads();
+            res = raw[0];
+        }
+        if (live) {
+            bin_store_x<SB>(a, i, res, pol);
+            mn = res;
+            mx = res;
+        }
+        if (uni) {   // every live lane holds the same value R: the block's pair is (R, R)
+            if (threadIdx.x == 0) {
+                a.partial[b] = make_double2(res, res);
+                if (a.eacc) publish_minmax(a.eacc, res, res);
+            }
+        } else {
+            block_minmax_store<SB>(mn, mx, a.partial + b, a.eacc);
+        }
+        if (a.ts) bin_ts(a.ts, t0, t1);
+        return;
+    }
     if (live) {
         VT res = xi;
         if (!FLT || is_active(si, a.r)) {
