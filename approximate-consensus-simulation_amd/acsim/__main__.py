@@ -15,6 +15,9 @@
   python -m acsim run --graph scheduled.npz --set rule=pushsum --set missing_policy=hold
       (a file with a link schedule, graphs.save_csr(..., schedule=...): rules weighted and pushsum run
       on it, reported on stderr; push-sum keeps the mean on a schedule under "hold" only)
+  python -m acsim run --graph g.npz --set rule=pushsum --transit 3
+      (push-sum with messages in transit for up to 3 rounds, DESIGN.md §9, on the file's weights and link
+      schedule, reported on stderr)
   python -m acsim run --graph scheduled.npz --set rule=pushsum --split
       (push-sum with per-round splitting on the file's schedule, DESIGN.md §9: no weights, no held
       state, and the mean is kept; reported on stderr)
@@ -62,7 +65,7 @@ def _grid(specs):
     return grid
 
 
-def validate(cfg: Config, csr=None, weights=None, schedule=None, split=False) -> int:
+def validate(cfg: Config, csr=None, weights=None, schedule=None, split=False, transit=None) -> int:
     """Host-side §A.8 validation through the library (no GPU needed: acs_create validates first)."""
     lib = _abi.load_library()
     c = cfg.to_c()
@@ -75,6 +78,16 @@ def validate(cfg: Config, csr=None, weights=None, schedule=None, split=False) ->
         rc = lib.acs_create_csr_split(C.byref(c), rp.ctypes.data_as(C.POINTER(C.c_uint64)),
                                       ci.ctypes.data_as(C.POINTER(C.c_uint32)), int(period),
                                       av.ctypes.data_as(C.POINTER(C.c_uint32)), 0, C.byref(h))
+    elif csr is not None and weights is not None and transit is not None:
+        rp, ci = np.ascontiguousarray(csr[0], dtype=np.uint64), np.ascontiguousarray(csr[1], dtype=np.uint32)
+        ws, we = (np.ascontiguousarray(w, dtype=np.float64) for w in weights)
+        av = None if schedule is None else np.ascontiguousarray(schedule[1], dtype=np.uint32)
+        dp = C.POINTER(C.c_double)
+        rc = lib.acs_create_csr_transit(C.byref(c), rp.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                        ci.ctypes.data_as(C.POINTER(C.c_uint32)), ws.ctypes.data_as(dp),
+                                        we.ctypes.data_as(dp), 0 if schedule is None else int(schedule[0]),
+                                        None if av is None else av.ctypes.data_as(C.POINTER(C.c_uint32)), int(transit),
+                                        0, C.byref(h))
     elif csr is not None and weights is not None and schedule is not None:
         rp, ci = csr
         ws, we = (np.ascontiguousarray(w, dtype=np.float64) for w in weights)
@@ -119,6 +132,9 @@ def main(argv=None) -> int:
         p.add_argument("--graph", metavar="FILE.npz", help="user CSR graph (acsim.graphs.load_csr)")
         p.add_argument("--split", action="store_true",
                        help="rule pushsum with per-round splitting on the graph file's link schedule (no weights)")
+        p.add_argument("--transit", type=int, metavar="D",
+                       help="rule pushsum with messages in transit for up to D rounds (0 .. 64), on the graph file's "
+                            "weights and link schedule")
         if name in ("run", "sweep"):
             p.add_argument("--out")
         if name == "sweep":
@@ -132,6 +148,13 @@ def main(argv=None) -> int:
     csr = weights = schedule = None
     if a.split and not a.graph:
         ap.error("--split needs --graph")
+    if a.transit is not None:
+        if not a.graph:
+            ap.error("--transit needs --graph")
+        if a.split:
+            ap.error("--transit is not served with --split")
+        if not 0 <= a.transit <= _abi.TRANSIT_MAX:
+            ap.error(f"--transit must be in 0 .. {_abi.TRANSIT_MAX}")
     if a.graph:
         from .config import _enum
         from .graphs import load_csr
@@ -173,9 +196,16 @@ def main(argv=None) -> int:
             except ValueError as e:
                 if "no link schedule" not in str(e):
                     raise
+                if a.transit is not None:
+                    print(f"pushsum: {a.graph} has no link schedule, every link is up in every round", file=sys.stderr)
+        if a.transit is not None:
+            if _enum("rule", cfg.rule) != _abi.RULE_PUSHSUM:
+                ap.error("--transit needs --set rule=pushsum")
+            print(f"pushsum: transit {a.transit}: a message arrives up to {a.transit} rounds after it is sent, its mass "
+                  "in transit until then", file=sys.stderr)
         cfg = cfg.replace(topology="csr", n_nodes=int(csr[0].size - 1))
     if a.cmd == "validate":
-        rc = validate(cfg, csr, weights, schedule, split=a.split)
+        rc = validate(cfg, csr, weights, schedule, split=a.split, transit=a.transit)
         if rc == 0:
             print("ok")
         return rc
@@ -183,7 +213,7 @@ def main(argv=None) -> int:
         from .io import save_result
         from .sim import simulate
         res = simulate(cfg, device=a.device, return_values=bool(a.out), csr=csr, weights=weights, schedule=schedule,
-                       split=a.split)
+                       split=a.split, transit=a.transit)
         from .sweep import summarize
         print(json.dumps(summarize(cfg, res)))
         if a.out:
@@ -191,7 +221,7 @@ def main(argv=None) -> int:
         return 0
     from .sweep import sweep
     rows = sweep(cfg, _grid(a.grid), out_dir=a.out, device=a.device, csr=csr, weights=weights, schedule=schedule,
-                 split=a.split)
+                 split=a.split, transit=a.transit)
     for r in rows:
         print(json.dumps(r))
     return 0

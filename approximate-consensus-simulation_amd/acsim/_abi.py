@@ -29,6 +29,7 @@ F64, F32 = 0, 1
 MISSING_SELF, MISSING_OMIT = 0, 1
 MISSING_HOLD = 2   # rule PUSHSUM only: a dropped message's mass waits on the link
 SCHEDULE_MAX_PERIOD = 32   # link schedules: one uint32 mask per CSR slot
+TRANSIT_MAX = 64           # push-sum with messages in transit: the largest transit bound
 
 STREAM_INIT, STREAM_DROP, STREAM_FAULTSET, STREAM_CRASH_ROUND = 0, 1, 2, 3
 STREAM_CRASH_PARTIAL, STREAM_BYZ, STREAM_GRAPH = 4, 5, 6
@@ -121,6 +122,10 @@ def _declare(lib: C.CDLL) -> None:
         "acs_get_link_schedule": (i32, [vp, P(u32), P(u32), u64]),
         "acs_create_csr_split": (i32, [P(AcsConfig), P(u64), P(u32), u32, P(u32), i32, P(vp)]),
         "acs_get_split_shares": (i32, [vp, P(C.c_double), u64]),
+        "acs_create_csr_transit": (i32, [P(AcsConfig), P(u64), P(u32), P(C.c_double), P(C.c_double), u32, P(u32),
+                                         u32, i32, P(vp)]),
+        "acs_get_pushsum_transit": (i32, [vp, u64, vp, vp, u64]),
+        "acs_set_pushsum_transit": (i32, [vp, vp, vp, u64]),
         "acs_comm_id_size": (i32, []),
         "acs_get_comm_id": (i32, [vp, u64]),
         "acs_create_partitioned": (i32, [P(AcsConfig), i32, i32, i32, vp, u64, P(vp)]),

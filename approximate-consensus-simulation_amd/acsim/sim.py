@@ -45,7 +45,7 @@ class Simulator:
 
     def __init__(self, cfg: Config | str, device: int = 0, backend: str = "hip",
                  partitions: int = 1, rank: int = 0, comm_id: Optional[bytes] = None,
-                 csr=None, weights=None, schedule=None, split=False):
+                 csr=None, weights=None, schedule=None, split=False, transit=None):
         """partitions > 1 node-partitions one RANDOM_REGULAR instance: with
         comm_id (RCCL unique id from acsim.distributed) this handle is `rank`'s partition on
         `device`; without it all partitions are simulated on `device` with private x copies
@@ -63,7 +63,13 @@ class Simulator:
         split=True with csr and rule="pushsum", and no weights ("Push-sum with per-round
         splitting"): in every round a sender divides its pair over itself and its links that are up
         in that round, so the mean is kept on any schedule with no held state.  Without a schedule
-        every link is up in every round (graphs.full_schedule(nnz, 1))."""
+        every link is up in every round (graphs.full_schedule(nnz, 1)).
+
+        transit=D (an integer 0 .. 64) with csr, weights and rule="pushsum" ("Push-sum with
+        messages in transit"): a message sent in round r arrives in round r + delta, delta drawn per slot and
+        round from 0 .. D, and until then its mass is in transit on the link, so the run still finds the
+        mean.  A schedule may be given too.  transit=None (the default) is the handle without delays;
+        transit=0 computes the same values through the transit kernels."""
         if isinstance(cfg, str):
             cfg = preset(cfg)
         if backend != "hip":
@@ -82,6 +88,17 @@ class Simulator:
             raise ValueError("split=True needs a csr graph")
         if schedule is not None and (csr is None or (weights is None and not split)):
             raise ValueError("a link schedule needs a csr graph with weights (rule 'weighted' or 'pushsum')")
+        self._transit = None
+        if transit is not None:
+            if isinstance(transit, bool) or int(transit) != transit:
+                raise ValueError("transit must be an integer")
+            if csr is None or weights is None:
+                raise ValueError("transit needs a csr graph with weights (rule 'pushsum')")
+            if split:
+                raise ValueError("transit is not served with split=True")
+            if not 0 <= int(transit) <= _abi.TRANSIT_MAX:
+                raise ValueError(f"transit must be in [0, {_abi.TRANSIT_MAX}]")
+            self._transit = int(transit)
         if split:   # rule="pushsum" with per-round splitting (acs_create_csr_split)
             from .graphs import check_schedule, full_schedule
             rp = np.ascontiguousarray(csr[0], dtype=np.uint64)
@@ -106,7 +123,17 @@ class Simulator:
                 raise ValueError("weights must be (w_self[n_nodes], w_edge[len(colidx)])")
             self._nnz = int(ci.size)
             dp = C.POINTER(C.c_double)
-            if schedule is not None:   # acs_create_csr_scheduled checks the period and the masks' bits
+            if self._transit is not None:   # push-sum with messages in transit (acs_create_csr_transit)
+                period, av = 0, None
+                if schedule is not None:
+                    from .graphs import check_schedule
+                    period, av = check_schedule(rp, schedule[0], schedule[1], values=False)
+                rc = self._lib.acs_create_csr_transit(
+                    C.byref(self._c), rp.ctypes.data_as(C.POINTER(C.c_uint64)), ci.ctypes.data_as(C.POINTER(C.c_uint32)),
+                    ws.ctypes.data_as(dp), we.ctypes.data_as(dp), period,
+                    None if av is None else av.ctypes.data_as(C.POINTER(C.c_uint32)), self._transit, int(device),
+                    C.byref(h))
+            elif schedule is not None:   # acs_create_csr_scheduled checks the period and the masks' bits
                 from .graphs import check_schedule
                 period, av = check_schedule(rp, schedule[0], schedule[1], values=False)
                 rc = self._lib.acs_create_csr_scheduled(
@@ -286,15 +313,53 @@ class Simulator:
             raise ValueError("h and k must have the same size")
         self._chk(self._lib.acs_set_pushsum_links(self._h, arrs[0].ctypes.data, arrs[1].ctypes.data, arrs[0].size))
 
+    @property
+    def transit_max(self):
+        """The transit bound D of a handle made with transit=D, else None."""
+        return self._transit
+
+    def pushsum_transit(self, instance: int = 0):
+        """(h[D, nnz], k[D, nnz]) of one instance of a handle made with transit=D: plane d
+        is what round R + d will deliver on every slot from messages already sent, R the instance's own
+        executed rounds."""
+        if self._transit is None:
+            raise ValueError("pushsum_transit needs a handle made with transit=D")
+        D, nnz = self._transit, getattr(self, "_nnz", 0)
+        h = np.empty((D, nnz), dtype=self.value_dtype)
+        k = np.empty((D, nnz), dtype=self.value_dtype)
+        self._chk(self._lib.acs_get_pushsum_transit(self._h, int(instance), h.ctypes.data, k.ctypes.data, h.size))
+        return h, k
+
+    def set_pushsum_transit(self, h: np.ndarray, k: np.ndarray) -> None:
+        """Set the mass in transit, B*D*nnz values each (instance-major, then plane-major as
+        pushsum_transit returns them).  set_state and set_pushsum_state empty the planes: a resume with
+        mass in flight calls this after."""
+        if self._transit is None:
+            raise ValueError("set_pushsum_transit needs a handle made with transit=D")
+        arrs = []
+        for v in (h, k):
+            v = np.asarray(v)
+            if self.value_dtype == np.float32 and v.dtype != np.float32 and not np.array_equal(
+                    v.astype(np.float32).astype(v.dtype), v):
+                raise ValueError("fp32 set_pushsum_transit: values must be exactly representable in binary32")
+            arrs.append(np.ascontiguousarray(v, dtype=self.value_dtype).reshape(-1))
+        if arrs[0].size != arrs[1].size:
+            raise ValueError("h and k must have the same size")
+        self._chk(self._lib.acs_set_pushsum_transit(self._h, arrs[0].ctypes.data, arrs[1].ctypes.data, arrs[0].size))
+
     def pushsum_mass(self, instance: int = 0):
         """(fsum(s) + fsum(h), fsum(z) + fsum(k)) of one instance as Python floats: the mass on the
-        nodes plus the mass held on the links (missing_policy="hold"; without it the node sums
-        alone).  With column sums of 1 the second member stays N under "hold"."""
+        nodes plus the mass held on the links (missing_policy="hold") or in transit (transit=D);
+        without either the node sums alone.  With column sums of 1 and no loss the second member
+        stays N under "hold" and with transit."""
         s, z = self.pushsum_state(instance)
         ms, mz = math.fsum(s.tolist()), math.fsum(z.tolist())
         if self._hold:
             h, k = self.pushsum_links(instance)
             ms, mz = ms + math.fsum(h.tolist()), mz + math.fsum(k.tolist())
+        if self._transit:
+            h, k = self.pushsum_transit(instance)
+            ms, mz = ms + math.fsum(h.reshape(-1).tolist()), mz + math.fsum(k.reshape(-1).tolist())
         return ms, mz
 
     def fault_status(self) -> np.ndarray:
@@ -358,7 +423,7 @@ class Simulator:
 
 def simulate(cfg: Config | str, backend: str = "hip", device: int = 0,
              devices: Optional[Sequence[int]] = None, return_values: bool = True,
-             csr=None, weights=None, schedule=None, split=False) -> Result:
+             csr=None, weights=None, schedule=None, split=False, transit=None) -> Result:
     """Run one configuration to termination and return its results."""
     if devices is not None:
         devices = list(devices)
@@ -367,7 +432,7 @@ def simulate(cfg: Config | str, backend: str = "hip", device: int = 0,
                              "processes with acsim.distributed (one rank per GPU)")
         device = devices[0]
     with Simulator(cfg, device=device, backend=backend, csr=csr, weights=weights, schedule=schedule,
-                   split=split) as sim:
+                   split=split, transit=transit) as sim:
         res = sim.run()
         x = None
         if return_values:

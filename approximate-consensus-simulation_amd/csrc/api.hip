@@ -119,6 +119,130 @@ int acs_create_csr_split(const acs_config* cfg, const uint64_t* rowptr, const ui
     return create_impl(cfg, device, 1, 0, nullptr, 0, out, rowptr, colidx, nullptr, nullptr, &sched);
 }
 
+int acs_create_csr_transit(const acs_config* cfg, const uint64_t* rowptr, const uint32_t* colidx, const double* w_self,
+                           const double* w_edge, uint32_t period, const uint32_t* avail, uint32_t transit_max, int device,
+                           acs_sim** out) {
+    if (out) *out = nullptr;
+    if (!cfg || cfg->topology != ACS_TOPO_CSR) return fail(ACS_EINVAL, "config topology must be ACS_TOPO_CSR");
+    if (cfg->rule != ACS_RULE_PUSHSUM)
+        return fail(ACS_EUNSUPPORTED, "messages in transit are served for rule PUSHSUM (got rule %u): rule WEIGHTED "
+                                      "delays values with delay_max", cfg->rule);
+    if (!rowptr || !colidx) return fail(ACS_EINVAL, "null CSR arrays");
+    if (!w_self || !w_edge) return fail(ACS_EINVAL, "null weight arrays");
+    if (!out) return fail(ACS_EINVAL, "null out");
+    if (transit_max > kTransitMax) return fail(ACS_EINVAL, "transit_max must be <= %u (got %u)", kTransitMax, transit_max);
+    if (period == 0 && avail) return fail(ACS_EINVAL, "a link schedule needs period >= 1 (no schedule: 0, NULL)");
+    if (int rc = validate(cfg)) return rc;   // (delay_max > 0 is refused there: the two delay models do not mix)
+    if (cfg->missing_policy == ACS_MISSING_HOLD)
+        return fail(ACS_EUNSUPPORTED, "push-sum with messages in transit does not serve missing_policy = HOLD yet: a gone "
+                                      "message's mass is lost, as under OMIT");
+    if (cfg->dtype == ACS_F32 && cfg->max_rounds > transit_f32_max_rounds(transit_max))
+        return fail(ACS_EINVAL, "PUSHSUM in fp32 with transit_max = %u needs max_rounds <= 2^26 / (16 + transit_max) = %u "
+                                "(binary32 sums stay finite, DESIGN.md §9)", transit_max, transit_f32_max_rounds(transit_max));
+    const LinkSchedule sched{period, avail};   // (checked with the arrays: sched_check.hpp)
+    return create_impl(cfg, device, 1, 0, nullptr, 0, out, rowptr, colidx, w_self, w_edge, period ? &sched : nullptr,
+                       (int)transit_max);
+}
+
+// The instance's relative plane d = 0 .. tmax - 1 (what round R + d delivers, R its executed rounds)
+// is ring plane (R + d) mod (tmax + 1): two runs of whole planes, [c, first) and [0, tmax - first)
+// with c = R mod (tmax + 1).  The plane left out, (R + tmax) mod (tmax + 1), is the one round R - 1
+// delivered and emptied.
+struct TransitRuns {
+    uint32_t c, first;   // ring plane of relative plane 0; relative planes in the first run
+};
+static TransitRuns transit_runs(const acs_sim* s, uint32_t rounds) {
+    const uint32_t np = s->tmax + 1, c = rounds % np;
+    return TransitRuns{c, np - c < s->tmax ? np - c : s->tmax};
+}
+
+int acs_get_pushsum_transit(acs_sim* s, uint64_t b, void* h_out, void* k_out, uint64_t n) {
+    if (!s) return fail(ACS_EINVAL, "null handle");
+    if (!s->transit) return fail(ACS_EINVAL, "acs_get_pushsum_transit: not a handle of acs_create_csr_transit");
+    const uint64_t need = (uint64_t)s->tmax * s->nnz;
+    if (b >= s->B || n < need || ((!h_out || !k_out) && need) || (s->tmax == 0 && n != 0))
+        return fail(ACS_EINVAL, "bad get_pushsum_transit arguments (instance < B, n >= transit_max * nnz = %llu; "
+                                "n = 0 on a transit_max = 0 handle)", (unsigned long long)need);
+    if (!need) return ACS_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    InstState e;
+    HIP_TRY(hipMemcpyAsync(&e, s->st + b, sizeof e, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    const TransitRuns t = transit_runs(s, e.rounds);
+    const uint64_t pb = plane_bytes(s);
+    const char* ring = static_cast<const char*>(s->ring) + b * (s->tmax + 1) * pb;
+    std::vector<unsigned char> h(need * 2 * s->es);
+    HIP_TRY(hipMemcpyAsync(h.data(), ring + t.c * pb, t.first * pb, hipMemcpyDeviceToHost, s->stream));
+    if (t.first < s->tmax)
+        HIP_TRY(hipMemcpyAsync(h.data() + t.first * pb, ring, (s->tmax - t.first) * pb, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (s->f32) {
+        const float* p = reinterpret_cast<const float*>(h.data());
+        for (uint64_t q = 0; q < need; ++q) {
+            static_cast<float*>(h_out)[q] = p[2 * q];
+            static_cast<float*>(k_out)[q] = p[2 * q + 1];
+        }
+    } else {
+        const double* p = reinterpret_cast<const double*>(h.data());
+        for (uint64_t q = 0; q < need; ++q) {
+            static_cast<double*>(h_out)[q] = p[2 * q];
+            static_cast<double*>(k_out)[q] = p[2 * q + 1];
+        }
+    }
+    return ACS_OK;
+}
+
+int acs_set_pushsum_transit(acs_sim* s, const void* hv, const void* kv, uint64_t n) {
+    if (!s) return fail(ACS_EINVAL, "null handle");
+    if (!s->transit) return fail(ACS_EINVAL, "acs_set_pushsum_transit: not a handle of acs_create_csr_transit");
+    const uint64_t per = (uint64_t)s->tmax * s->nnz;
+    if (n != s->B * per)
+        return fail(ACS_EINVAL, "set_pushsum_transit needs B * transit_max * nnz = %llu values in h and in k (got %llu)",
+                    (unsigned long long)(s->B * per), (unsigned long long)n);
+    if ((!hv || !kv) && n) return fail(ACS_EINVAL, "null argument");
+    if (!n) return ACS_OK;
+    // mass in transit takes the caps of s and z ("mass bound"); -0.0 is stored as +0.0
+    std::vector<unsigned char> h(n * 2 * s->es);
+    if (s->f32) {
+        float* p = reinterpret_cast<float*>(h.data());
+        for (uint64_t e = 0; e < n; ++e) {
+            const float a = static_cast<const float*>(hv)[e], k = static_cast<const float*>(kv)[e];
+            if (!(fabsf(a) <= kPushsumMaxAbs32))
+                return fail(ACS_EINVAL, "set_pushsum_transit: h[%llu] is not finite or |h| > 1e26", (unsigned long long)e);
+            if (!(k >= 0.0f && k <= kPushsumMaxAbs32))
+                return fail(ACS_EINVAL, "set_pushsum_transit: k[%llu] must be finite, in [0, 1e26]", (unsigned long long)e);
+            p[2 * e] = a + 0.0f;
+            p[2 * e + 1] = k + 0.0f;
+        }
+    } else {
+        double* p = reinterpret_cast<double*>(h.data());
+        for (uint64_t e = 0; e < n; ++e) {
+            const double a = static_cast<const double*>(hv)[e], k = static_cast<const double*>(kv)[e];
+            if (!(fabs(a) <= kPushsumMaxAbs64))
+                return fail(ACS_EINVAL, "set_pushsum_transit: h[%llu] is not finite or |h| > 1e290", (unsigned long long)e);
+            if (!(k >= 0.0 && k <= kPushsumMaxAbs64))
+                return fail(ACS_EINVAL, "set_pushsum_transit: k[%llu] must be finite, in [0, 1e290]", (unsigned long long)e);
+            p[2 * e] = a + 0.0;
+            p[2 * e + 1] = k + 0.0;
+        }
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    std::vector<InstState> v;
+    if (int rc = read_states(s, v)) return rc;
+    const uint64_t pb = plane_bytes(s);
+    HIP_TRY(hipMemsetAsync(s->ring, 0, ring_bytes(s), s->stream));   // (the plane no relative plane maps to stays empty)
+    for (uint64_t b = 0; b < s->B; ++b) {
+        const TransitRuns t = transit_runs(s, v[b].rounds);
+        char* ring = static_cast<char*>(s->ring) + b * (s->tmax + 1) * pb;
+        const unsigned char* src = h.data() + b * s->tmax * pb;
+        HIP_TRY(hipMemcpyAsync(ring + t.c * pb, src, t.first * pb, hipMemcpyHostToDevice, s->stream));
+        if (t.first < s->tmax)
+            HIP_TRY(hipMemcpyAsync(ring, src + t.first * pb, (s->tmax - t.first) * pb, hipMemcpyHostToDevice, s->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream));   // h outlives the copies
+    return ACS_OK;
+}
+
 int acs_get_split_shares(acs_sim* s, double* out, uint64_t n) {
     if (!s || !out) return fail(ACS_EINVAL, "null argument");
     if (!s->split) return fail(ACS_EINVAL, "acs_get_split_shares: not a handle of acs_create_csr_split");
@@ -410,6 +534,8 @@ int acs_set_state(acs_sim* s, uint32_t round, const void* x, uint64_t n) {
                                      s->stream));
     if (s->hold)      // and every link empty (a resume with held mass calls acs_set_pushsum_links next)
         HIP_TRY(hipMemsetAsync(s->links, 0, links_bytes(s), s->stream));
+    if (s->transit)   // and nothing in transit (a resume with mass in flight calls acs_set_pushsum_transit next)
+        HIP_TRY(hipMemsetAsync(s->ring, 0, ring_bytes(s), s->stream));
     return init_state(s, round);
 }
 
@@ -478,6 +604,7 @@ int acs_set_pushsum_state(acs_sim* s, uint32_t round, const void* sv, const void
         HIP_TRY(launch_pushsum_offer(pairs_at(s, round), share_at(s, round), offers_at(s, round), s->B, s->N, s->f32,
                                      s->stream));
     if (s->hold) HIP_TRY(hipMemsetAsync(s->links, 0, links_bytes(s), s->stream));   // as acs_set_state
+    if (s->transit) HIP_TRY(hipMemsetAsync(s->ring, 0, ring_bytes(s), s->stream));
     return init_state(s, round);   // (synchronises: h outlives the copy)
 }
 

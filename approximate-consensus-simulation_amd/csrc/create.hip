@@ -99,7 +99,9 @@ int validate(const acs_config* c) {
         if (c->loss_p > 0.0 && c->missing_policy == ACS_MISSING_SELF)
             return fail(ACS_EINVAL, "PUSHSUM with loss_p > 0 needs missing_policy = OMIT: SELF would put the "
                                     "receiver's own pair in place of a lost message and create mass");
-        if (c->delay_max > 0) return fail(ACS_EUNSUPPORTED, "PUSHSUM does not serve delay_max > 0 yet");
+        if (c->delay_max > 0)
+            return fail(ACS_EUNSUPPORTED, "PUSHSUM does not serve delay_max > 0: a stale read of (s, z) pairs creates and "
+                                          "destroys mass; acs_create_csr_transit delays messages with their mass in transit");
         if (c->dtype == ACS_F32 && c->max_rounds > kPushsumF32MaxRounds)
             return fail(ACS_EINVAL, "PUSHSUM in fp32 needs max_rounds <= 2^22 (binary32 sums stay finite, DESIGN.md §9)");
     }
@@ -218,6 +220,7 @@ void release(acs_sim* s) {
     (void)hipFree(s->well);
     (void)hipFree(s->pairs);
     (void)hipFree(s->links);
+    (void)hipFree(s->ring);
     (void)hipFree(s->avail);
     (void)hipFree(s->avell);
     (void)hipFree(s->share);
@@ -681,9 +684,11 @@ static std::string kernel_name_of(const acs_sim* s) {
         if (s->bin_sb != kBinSB) nm += " sb" + std::to_string(s->bin_sb);
     } else if (s->csr_var) {
         const std::string w = "<" + std::to_string(s->d) + (s->sched ? ",csr,sched>" : ",csr>");   // (SCHED instantiations)
-        // (k_round_pushsum_hold: the reported name of k_round_pushsum's HOLD = true instantiation)
+        // (k_round_pushsum_hold, k_round_pushsum_transit: the reported names of k_round_pushsum's kLinkHold and
+        // kLinkTransit instantiations)
         nm = s->split    ? "k_round_pushsum_split<" + std::to_string(s->d) + ",csr>"
            : s->hold     ? "k_round_pushsum_hold" + w
+           : s->transit  ? "k_round_pushsum_transit" + w
            : s->pushsum  ? "k_round_pushsum" + w
            : s->weighted ? "k_round_weighted" + w
                          : "k_round_regular<" + std::to_string(s->d) + "," + std::to_string(c.trim) + ",csr>";
@@ -717,6 +722,10 @@ static int finish_handle(acs_sim* s, const CreateOptions& o, const void* comm_id
     if (s->hold) {   // every link starts empty: (+0.0, +0.0)
         STAGE_TRY(hipMalloc(&s->links, links_bytes(s)));
         STAGE_TRY(hipMemsetAsync(s->links, 0, links_bytes(s), s->stream));
+    }
+    if (s->transit) {   // nothing is in transit at round 0
+        STAGE_TRY(hipMalloc(&s->ring, ring_bytes(s)));
+        STAGE_TRY(hipMemsetAsync(s->ring, 0, ring_bytes(s), s->stream));
     }
     for (Part& q : s->parts)
         STAGE_TRY(launch_init_values(q.x[0], s->B, s->N, s->mp.key, c.instance_offset, s->f32, s->stream));
@@ -796,7 +805,7 @@ static int check_arguments(const acs_config* cfg, int device, int nranks, int ra
 
 // The handle's fields that follow from the config, the partition arguments and the path alone.
 static acs_sim* new_handle(const acs_config& c, int device, int nranks, int rank, bool partitioned, bool virt,
-                           const PathChoice& pc, const CsrCheck& chk, const LinkSchedule* h_sched) {
+                           const PathChoice& pc, const CsrCheck& chk, const LinkSchedule* h_sched, int transit_max) {
     acs_sim* s = new acs_sim();
     s->c = c;
     s->device = device;
@@ -814,6 +823,8 @@ static acs_sim* new_handle(const acs_config& c, int device, int nranks, int rank
     s->pushsum = c.rule == ACS_RULE_PUSHSUM;   // (weights as for WEIGHTED, one more rule)
     s->weighted = c.rule == ACS_RULE_WEIGHTED || s->pushsum;
     s->hold = s->pushsum && c.missing_policy == ACS_MISSING_HOLD;   // (validate: HOLD only with PUSHSUM)
+    s->transit = transit_max >= 0;   // (acs_create_csr_transit: rule PUSHSUM, never HOLD)
+    s->tmax = s->transit ? (uint32_t)transit_max : 0u;
     s->nnz = chk.nnz;
     s->sched = h_sched != nullptr;
     s->period = h_sched ? h_sched->period : 0;
@@ -844,7 +855,7 @@ static acs_sim* new_handle(const acs_config& c, int device, int nranks, int rank
 
 int create_impl(const acs_config* cfg, int device, int nranks, int rank, const void* comm_id, uint64_t id_len,
                 acs_sim** out, const uint64_t* h_rowptr, const uint32_t* h_colidx, const double* h_wself,
-                const double* h_wedge, const LinkSchedule* h_sched) {
+                const double* h_wedge, const LinkSchedule* h_sched, int transit_max) {
     *out = nullptr;
     // 1. host checks and 2. path choice, before any handle exists
     CsrCheck chk;
@@ -856,7 +867,7 @@ int create_impl(const acs_config* cfg, int device, int nranks, int rank, const v
     if (int rc = choose_path(*cfg, opt, partitioned, chk.mmax, h_rowptr, pc)) return rc;
 
     RoctxRange range("acs: create (graph, plan, fault schedule, x0)");
-    acs_sim* s = new_handle(*cfg, device, nranks, rank, partitioned, partitioned && !comm_id, pc, chk, h_sched);
+    acs_sim* s = new_handle(*cfg, device, nranks, rank, partitioned, partitioned && !comm_id, pc, chk, h_sched, transit_max);
     // 3. - 7.: the order matters in three places.  eacc (alloc_state) exists before any
     // binned_build, whose bin_desc reads it; the fault status is built before the plans, whose fix-up
     // list reads it; and `binned` is decided (decide_binned) before the fp32 crash-rank table.

@@ -13,6 +13,9 @@
 //               dtype (double2 / float2); instance b at round r lives in pairs[r & 1], beside x
 //   links     : rule PUSHSUM with missing_policy = HOLD only: one buffer [B][nnz] of
 //               held (h, k) pairs in CSR slot order, updated in place by each slot's receiver
+//   ring      : rule PUSHSUM with messages in transit only: transit_max + 1 planes
+//               [B][transit_max + 1][nnz] of pending (h, k) pairs in CSR slot order; plane q mod
+//               (transit_max + 1) holds what round q delivers, updated in place by each slot's receiver
 //   share, offers : rule PUSHSUM with per-round splitting only: the share table
 //               [period][N] of the config dtype, and two buffers [B][N] of offers (share * pair) by
 //               round parity, beside pairs; such a handle has no wself / wedge / well and no links
@@ -122,6 +125,13 @@ struct RoundArgs {
     const void* oin;
     void* oout;
     const void* share_next;
+    // rule PUSHSUM with messages in transit (handles of acs_create_csr_transit): a ring
+    // of trn_np = transit_max + 1 planes of pending (h, k) pairs per instance, [B][trn_np][lnk_stride]
+    // of double2 (fp32: float2) in slot order; the cell of arrival round q is plane q mod trn_np and
+    // trn_cur = r mod trn_np is the plane this round delivers.  Read and written in place by the
+    // slot's receiver.  nullptr for every other handle.
+    void* trn;
+    uint32_t trn_cur, trn_np;
 };
 constexpr uint32_t kEaccSlots = 32, kEaccStride = 16;       // eacc pairs, u64 words between pairs
 constexpr uint32_t kEaccWords = kEaccSlots * kEaccStride;   // eacc words of one round parity
@@ -233,6 +243,8 @@ hipError_t launch_avail_to_ell(const uint64_t* rowptr, const uint32_t* avail, co
 // hold: the handle runs missing_policy = HOLD (the kernel's HOLD instantiation): a dropped message's
 // mass stays on its link (a.lnk, updated in place) and arrives with the next message that gets
 // through.  hipErrorInvalidValue unless a.lnk is set exactly when hold is.
+// a.trn set (never with hold): the kernel's transit instantiation, messages delivered delta rounds
+// after they are sent through the ring of pending pairs.
 hipError_t launch_round_pushsum(const RoundArgs& a, bool hold, uint64_t B, uint32_t nblk_fast, hipStream_t s);
 // pairs[k] = (x[k], 1) for n values (create, acs_set_state)
 hipError_t launch_pushsum_fill(const void* x, void* pairs, uint64_t n, bool f32, hipStream_t s);

@@ -161,6 +161,13 @@ struct acs_sim {
     // kernels update it in place.  Null for every other handle.
     bool hold = false;
     void* links = nullptr;
+    // ... with messages in transit (handles of acs_create_csr_transit, never HOLD): a
+    // message arrives up to tmax rounds after it is sent, and waits in a ring of tmax + 1 planes
+    // [B][tmax + 1][nnz] of (h, k) pairs in slot order, zeroed at create; the cell of arrival round q
+    // is in plane q mod (tmax + 1).  Null for every other handle.
+    bool transit = false;
+    uint32_t tmax = 0;
+    void* ring = nullptr;
     // link schedule ("Link schedules"; handles of acs_create_csr_scheduled): the slots'
     // availability masks, shared by all instances, held twice: in slot order (the public view, and
     // the one k_round_generic indexes) and, on the per-lane path, in well's order (0 in absent columns)
@@ -197,6 +204,10 @@ struct acs_sim {
 static constexpr double kPushsumMaxAbs64 = 1e290;
 static constexpr float kPushsumMaxAbs32 = 1e26f;
 static constexpr uint32_t kPushsumF32MaxRounds = 1u << 22;
+// ... with messages in transit: a pending value passes through up to transit_max further additions,
+// so the fp32 round limit is 2^26 / (16 + transit_max) (2^22 at transit_max = 0)
+static constexpr uint32_t kTransitMax = 64;
+static inline uint32_t transit_f32_max_rounds(uint32_t tmax) { return (1u << 26) / (16u + tmax); }
 
 // Host memory the device writes and the host polls (run summary, instance states): mapped into the
 // device's address space and explicitly COHERENT, so the device's system-scope release of the
@@ -233,6 +244,13 @@ static inline void* share_at(const acs_sim* s, uint32_t q) {
 }
 // rule PUSHSUM under HOLD: bytes of the link buffer (at least one pair, so the pointer is never null)
 static inline uint64_t links_bytes(const acs_sim* s) { return (s->B * s->nnz ? s->B * s->nnz : 1) * 2 * s->es; }
+// ... with messages in transit: bytes of one plane of one instance, and of the whole ring (at least
+// one pair, so the pointer is never null)
+static inline uint64_t plane_bytes(const acs_sim* s) { return s->nnz * 2 * s->es; }
+static inline uint64_t ring_bytes(const acs_sim* s) {
+    const uint64_t b = s->B * (s->tmax + 1) * plane_bytes(s);
+    return b ? b : 2 * s->es;
+}
 static inline uint64_t part_row0(const acs_sim* s, int p) { return (uint64_t)p * s->rows_per; }
 static inline uint64_t part_rows(const acs_sim* s, int p) {
     const uint64_t r0 = part_row0(s, p);
@@ -251,7 +269,7 @@ int validate(const acs_config* c);   // §A.8 constraints
 int create_impl(const acs_config* cfg, int device, int nranks, int rank, const void* comm_id, uint64_t id_len,
                 acs_sim** out, const uint64_t* h_rowptr = nullptr, const uint32_t* h_colidx = nullptr,
                 const double* h_wself = nullptr, const double* h_wedge = nullptr,
-                const LinkSchedule* h_sched = nullptr);
+                const LinkSchedule* h_sched = nullptr, int transit_max = -1);   // >= 0: acs_create_csr_transit
 void release(acs_sim* s);
 
 // ---- rounds.hip

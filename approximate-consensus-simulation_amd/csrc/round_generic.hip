@@ -137,7 +137,9 @@ __device__ __forceinline__ VT generic_entry(const RoundArgs& a, uint32_t lb, uin
 // VT = double, or float in fp32 mode
 // BLK threads per workgroup: 64 for receivers of at most 512 entries (one wave), 1024 above 2048
 // entries (the serial sort passes of one receiver are the kernel's tail), 256 otherwise.
-template <int BLK, typename VT>
+// TRANSIT: the instantiation for push-sum handles with messages in transit (a.trn; rule 6 alone, so
+// it holds nothing but that branch): the ring step would otherwise cost every rule registers.
+template <int BLK, typename VT, bool TRANSIT = false>
 __global__ __launch_bounds__(BLK) void k_round_generic(const RoundArgs a, uint32_t Pmax) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sh_raw[];
     VT* sh = reinterpret_cast<VT*>(sh_raw);   // [Pmax] entries + [Pmax] scratch
@@ -175,7 +177,7 @@ __global__ __launch_bounds__(BLK) void k_round_generic(const RoundArgs a, uint32
     while (P < m) P <<= 1;
     const VT lo = (VT)S->lo, hi = (VT)S->hi;
     const bool avg = a.rule == 0;
-    if (a.rule == 5) {
+    if (!TRANSIT && a.rule == 5) {
         // WEIGHTED (CSR rows): products p_e = (w_e * v_e) + 0.0 in one LDS half, weights
         // in the other, one entry-order tree sum each; an entry OMIT leaves out (and the padding
         // past m) adds +0.0 to both.  A zero weight sum (OMIT only) keeps x_i.
@@ -204,7 +206,7 @@ __global__ __launch_bounds__(BLK) void k_round_generic(const RoundArgs a, uint32
         }
         return;
     }
-    if (a.rule == 6) {
+    if (TRANSIT || a.rule == 6) {
         // PUSHSUM (CSR rows, no faults, no delays): ps_e = (w_e * s_e) + 0.0 in one LDS
         // half and pz_e = (w_e * z_e) + 0.0 in the other, one entry-order tree sum each, no
         // normalisation; a dropped message (and the padding past m) adds +0.0 to both.  z' = 0 keeps x_i.
@@ -215,11 +217,15 @@ __global__ __launch_bounds__(BLK) void k_round_generic(const RoundArgs a, uint32
         // missing_policy = HOLD (a.lnk; k_round_pushsum's HOLD instantiation): the slot's held pair takes the product
         // (hn = h_e + a, kn = k_e + c); a delivered message contributes (hn, kn) and empties the link,
         // a dropped one contributes +0.0 and leaves (hn, kn) on it.  In place: one thread per slot.
-        V2* lk = a.lnk ? reinterpret_cast<V2*>(a.lnk) + (uint64_t)lb * a.lnk_stride : nullptr;
+        V2* lk = !TRANSIT && a.lnk ? reinterpret_cast<V2*>(a.lnk) + (uint64_t)lb * a.lnk_stride : nullptr;
         // per-round splitting (a.oin; k_round_pushsum_split): an entry is its sender's offer as stored
         // (entry 0: the row's own), +0.0 on a slot that is down or dropped; the row's next offer is
         // stored with its pair.
-        const V2* __restrict__ oin = a.oin ? reinterpret_cast<const V2*>(a.oin) + lb * N : nullptr;
+        const V2* __restrict__ oin = !TRANSIT && a.oin ? reinterpret_cast<const V2*>(a.oin) + lb * N : nullptr;
+        // messages in transit (a.trn; k_round_pushsum's transit instantiation): the entry is the slot's cell
+        // of the plane this round delivers, which is then emptied; a message that is not gone joins
+        // that cell (delta = 0) or the cell of plane (r + delta) mod trn_np.  In place: one thread per slot.
+        V2* tr = TRANSIT ? reinterpret_cast<V2*>(a.trn) + (uint64_t)lb * a.trn_np * a.lnk_stride : nullptr;
         for (uint32_t e = threadIdx.x; e < P; e += BLK) {
             VT pe = VT(0), ze = VT(0);
             if (e < m) {
@@ -243,6 +249,32 @@ __global__ __launch_bounds__(BLK) void k_round_generic(const RoundArgs a, uint32
                     lk[slot] = keep;
                     pe = dropped ? VT(0) : hn;
                     ze = dropped ? VT(0) : kn;
+                } else if (tr && e != 0) {
+                    V2* cell = tr + (uint64_t)a.trn_cur * a.lnk_stride + slot;
+                    const V2 l = *cell;
+                    pe = l.x;
+                    ze = l.y;
+                    if (!dropped) {
+                        const VT wt = we[slot];
+                        const V2 v = pin[a.colidx[slot]];
+                        const VT pa = wt * v.x + VT(0), pc = wt * v.y + VT(0);
+                        const uint32_t dl = a.trn_np > 1 ? draw(mp.key, kStreamDelay, b, a.r, slot) % a.trn_np : 0u;
+                        if (dl == 0) {
+                            pe = l.x + pa;
+                            ze = l.y + pc;
+                        } else {
+                            uint32_t p = a.trn_cur + dl;
+                            if (p >= a.trn_np) p -= a.trn_np;
+                            V2* far = tr + (uint64_t)p * a.lnk_stride + slot;
+                            V2 g = *far;
+                            g.x = g.x + pa;
+                            g.y = g.y + pc;
+                            *far = g;
+                        }
+                    }
+                    V2 zero;
+                    zero.x = zero.y = VT(0);
+                    if (l.x != VT(0) || l.y != VT(0)) *cell = zero;   // (no cell ever holds -0.0)
                 } else if (!dropped) {
                     const VT wt = e == 0 ? ws[i] : we[slot];
                     const V2 v = pin[e == 0 ? i : a.colidx[slot]];
@@ -652,6 +684,12 @@ hipError_t launch_round_generic(const RoundArgs& a, uint64_t B, hipStream_t s, u
             if (e == hipSuccess)
                 e = hipFuncSetAttribute((const void*)k_round_generic<1024, double>,
                                         hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+            if (e == hipSuccess)
+                e = hipFuncSetAttribute((const void*)k_round_generic<256, double, true>,
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+            if (e == hipSuccess)
+                e = hipFuncSetAttribute((const void*)k_round_generic<1024, double, true>,
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
             status[dev] = e;
         });
         if (status[dev] != hipSuccess) return status[dev];
@@ -660,7 +698,11 @@ hipError_t launch_round_generic(const RoundArgs& a, uint64_t B, hipStream_t s, u
     const int blk = P <= 512 ? 64 : P <= 2048 ? 256 : 1024;   // (merge sort: P / 8 threads per pass)
 #define ACS_GEN_LAUNCH(BB)                                                                                         \
     {                                                                                                              \
-        if (a.f32)                                                                                                 \
+        if (a.trn && a.f32)                                                                                        \
+            hipLaunchKernelGGL((k_round_generic<BB, float, true>), grid, dim3(BB), lds, s, a, P);                  \
+        else if (a.trn)                                                                                            \
+            hipLaunchKernelGGL((k_round_generic<BB, double, true>), grid, dim3(BB), lds, s, a, P);                 \
+        else if (a.f32)                                                                                            \
             hipLaunchKernelGGL((k_round_generic<BB, float>), grid, dim3(BB), lds, s, a, P);                        \
         else                                                                                                       \
             hipLaunchKernelGGL((k_round_generic<BB, double>), grid, dim3(BB), lds, s, a, P);                       \

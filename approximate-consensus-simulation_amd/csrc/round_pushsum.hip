@@ -18,7 +18,7 @@
 //   - (min, max) of x^{r+1} reduced per block -> one partial (§A.8 epilogue).
 // Hub rows (deg[i] = kDegHub) are left to k_round_generic's rule-6 branch.
 //
-// HOLD = true is the rule under missing_policy = HOLD: robust ratio consensus by
+// LINK = kLinkHold is the rule under missing_policy = HOLD: robust ratio consensus by
 // running sums.  Mass that fails to cross a link is not lost: it waits on the link and arrives with
 // the next message that gets through.
 // Besides the (s, z) pair of every node, every CSR slot e = rowptr[i] + t of every instance holds a
@@ -37,6 +37,22 @@
 // whose value equals, bit for bit, what was loaded is skipped (a delivered message on an empty
 // link: every link of a lossless run).
 // Hub rows take the same steps in k_round_generic's rule-6 branch when RoundArgs carries links.
+//
+// LINK = kLinkTransit is the rule with messages in transit ("Push-sum with messages in
+// transit"; handles of acs_create_csr_transit): a message sent in round r on slot e arrives in round
+// r + delta, delta = draw(DELAY, b, r, e) mod (transit_max + 1), and until then its mass waits in
+// the ring a.trn: trn_np = transit_max + 1 planes [nnz] of (h, k) pairs per instance, the cell of
+// arrival round q in plane q mod trn_np.  With each weight group come the group's cells of the
+// plane this round delivers (a.trn_cur), as HOLD's links do.  Per sender entry that is not gone
+// (dropped, or down under a schedule: a gone message never enters transit, its mass is lost):
+//   a = (w_e * s_j) + 0.0, c = (w_e * z_j) + 0.0     the plain rule's products
+//   delta = 0: the loaded cell takes (a, c) in registers     one rounding each
+//   delta > 0: the cell of plane (r + delta) mod trn_np takes (a, c) in place (a load, a store)
+// The entry contributes its cell of the current plane, which then stores (+0.0, +0.0); a store whose
+// bits equal what was loaded is skipped.  A cell therefore folds its arrivals in ascending sending
+// round, from +0.0 (or from what acs_set_pushsum_transit put there).  The delta > 0 cell is never
+// the one being delivered (1 <= delta <= transit_max < trn_np), and every cell of slot e is touched
+// by e's receiver lane alone.
 #include "csr_lane.hpp"
 #include "resolve.hpp"
 #include "rules.hpp"
@@ -50,9 +66,12 @@ __device__ __forceinline__ bool same_bits(float u, float v) { return __float_as_
 // availability masks (a.avell, the weights' order); a slot that is down in this round is gone like
 // a dropped one (HOLD: it takes the dropped branch, so its mass waits on the link until the slot is
 // up again).
-template <int D, typename VT, bool SCHED, bool HOLD>
+enum : int { kLinkPlain = 0, kLinkHold = 1, kLinkTransit = 2 };   // what a message does on its link
+
+template <int D, typename VT, bool SCHED, int LINK>
 __global__ __launch_bounds__(kRegularBlock) void k_round_pushsum(const RoundArgs a) {
     static_assert(D % 4 == 0, "compiled widths are multiples of 4");
+    constexpr bool HOLD = LINK == kLinkHold, TRANSIT = LINK == kLinkTransit;
     constexpr int M = D + 1;
     constexpr int NQ = D / 4;
     using W4 = typename EllVec<VT>::w4;
@@ -79,6 +98,9 @@ __global__ __launch_bounds__(kRegularBlock) void k_round_pushsum(const RoundArgs
         // HOLD: this row's links, slots rp .. rp + dg - 1 of instance lb (rp + dg <= nnz = a.lnk_stride).
         // Formed here, before the id loads: inside the group loop it compiles to other code.
         [[maybe_unused]] V2* lk = HOLD ? reinterpret_cast<V2*>(a.lnk) + (uint64_t)lb * a.lnk_stride + rp : nullptr;
+        // TRANSIT: this row's cells of plane 0 of instance lb's ring; plane p is a.lnk_stride pairs on
+        [[maybe_unused]] V2* tr =
+            TRANSIT ? reinterpret_cast<V2*>(a.trn) + (uint64_t)lb * a.trn_np * a.lnk_stride + rp : nullptr;
         VT ps[M], pz[M];
         {
             uint32_t col[D];
@@ -144,6 +166,53 @@ __global__ __launch_bounds__(kRegularBlock) void k_round_pushsum(const RoundArgs
                     keep.x = dropped ? hn : VT(0);
                     keep.y = dropped ? kn : VT(0);
                     if (here && !(same_bits(keep.x, l[k].x) && same_bits(keep.y, l[k].y))) lk[t] = keep;
+                }
+            } else if constexpr (TRANSIT) {
+                V2* tc = tr + (uint64_t)a.trn_cur * a.lnk_stride;   // the plane round r delivers
+                V2 l[4], g[4];    // the group's cells of that plane, and of the planes its messages go to
+                uint32_t dst[4];  // the plane a message goes to (a.trn_cur: delivered now), kEllNone: gone
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    l[k].x = l[k].y = VT(0);
+                    if ((uint32_t)(4 * q + k) < dg) l[k] = tc[4 * q + k];
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int t = 4 * q + k;
+                    bool gone = (uint32_t)t >= dg;   // absent column: +0.0 in both sums, no cell
+                    if (!gone && mp.thr) gone = draw(mp.key, kStreamDrop, bG, r, rp + t) < mp.thr;
+                    if (SCHED) gone = gone || ((down >> k) & 1u);
+                    uint32_t p = gone ? kEllNone : a.trn_cur;
+                    if (!gone && a.trn_np > 1) {
+                        p += draw(mp.key, kStreamDelay, b, r, rp + t) % a.trn_np;
+                        if (p >= a.trn_np) p -= a.trn_np;
+                    }
+                    dst[k] = p;
+                    g[k].x = g[k].y = VT(0);
+                    if (p != kEllNone && p != a.trn_cur) g[k] = tr[(uint64_t)p * a.lnk_stride + t];
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int t = 4 * q + k;
+                    VT sv = ps[1 + t], zv = pz[1 + t];
+                    // (binary32, D = 32: the SLP vectoriser pairs neighbouring elements of ps for packed
+                    // multiplies and then leaves the whole array in scratch; the empty asm keeps them scalar)
+                    if constexpr (sizeof(VT) == 4) asm("" : "+v"(sv), "+v"(zv));
+                    const VT pa = wq[k] * sv + VT(0);
+                    const VT pc = wq[k] * zv + VT(0);
+                    const bool now = dst[k] == a.trn_cur;
+                    ps[1 + t] = now ? l[k].x + pa : l[k].x;   // (absent column: the cell read as +0.0)
+                    pz[1 + t] = now ? l[k].y + pc : l[k].y;
+                    if (dst[k] != kEllNone && !now) {
+                        V2 n;
+                        n.x = g[k].x + pa;
+                        n.y = g[k].y + pc;
+                        if (!(same_bits(n.x, g[k].x) && same_bits(n.y, g[k].y))) tr[(uint64_t)dst[k] * a.lnk_stride + t] = n;
+                    }
+                    V2 zero;
+                    zero.x = zero.y = VT(0);
+                    // (an absent column's l is +0.0: no store)
+                    if (!(same_bits(l[k].x, VT(0)) && same_bits(l[k].y, VT(0)))) tc[t] = zero;
                 }
             } else {
 #pragma unroll
@@ -218,16 +287,19 @@ hipError_t launch_pushsum_estimate(const void* pairs, void* x, uint64_t n, bool 
 hipError_t launch_round_pushsum(const RoundArgs& a, bool hold, uint64_t B, uint32_t nblk_fast, hipStream_t s) {
     if (!a.deg || !a.sw || !a.ell || !a.well || !a.wself || !a.rowptr || !a.pin || !a.pout || hold != (a.lnk != nullptr))
         return hipErrorInvalidValue;
+    if (a.trn && (hold || a.trn_np < 1 || a.trn_cur >= a.trn_np)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)nblk_fast, (unsigned)B);
     const dim3 block(kRegularBlock);
     const bool hit = csr_lane_select(a, [&](auto d, auto vt, auto sched) {
         constexpr int DD = decltype(d)::value;
         constexpr bool SCHED = decltype(sched)::value;
         using VT = decltype(vt);
-        if (hold)
-            hipLaunchKernelGGL((k_round_pushsum<DD, VT, SCHED, true>), grid, block, 0, s, a);
+        if (a.trn)
+            hipLaunchKernelGGL((k_round_pushsum<DD, VT, SCHED, kLinkTransit>), grid, block, 0, s, a);
+        else if (hold)
+            hipLaunchKernelGGL((k_round_pushsum<DD, VT, SCHED, kLinkHold>), grid, block, 0, s, a);
         else
-            hipLaunchKernelGGL((k_round_pushsum<DD, VT, SCHED, false>), grid, block, 0, s, a);
+            hipLaunchKernelGGL((k_round_pushsum<DD, VT, SCHED, kLinkPlain>), grid, block, 0, s, a);
     });
     return hit ? hipGetLastError() : hipErrorNotSupported;
 }

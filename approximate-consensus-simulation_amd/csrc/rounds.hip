@@ -164,6 +164,11 @@ static RoundArgs round_args(acs_sim* s, uint32_t r) {
         a.lnk = s->links;   // (HOLD handles only: null selects the plain rule in k_round_generic)
         a.lnk_stride = s->nnz;
     }
+    if (s->transit) {   // (the plane follows the round index, like the schedule's phase)
+        a.trn = s->ring;
+        a.trn_np = s->tmax + 1;
+        a.trn_cur = r % a.trn_np;
+    }
     if (s->split) {   // (this round's shares are in the offers already)
         a.oin = offers_at(s, r);
         a.oout = offers_at(s, r + 1);

@@ -33,7 +33,8 @@ extern "C" {
                                   likewise ACS_MISSING_HOLD and acs_get / acs_set_pushsum_links;
                                   likewise ACS_SCHEDULE_MAX_PERIOD, acs_create_csr_scheduled and
                                   acs_get_link_schedule; likewise acs_create_csr_split and
-                                  acs_get_split_shares) */
+                                  acs_get_split_shares; likewise acs_create_csr_transit and
+                                  acs_get / acs_set_pushsum_transit) */
 
 /* status codes */
 #define ACS_OK            0
@@ -250,6 +251,36 @@ int acs_create_csr_split(const acs_config* cfg, const uint64_t* rowptr, const ui
 /* The share table as the device holds it, phase-major: out[p * N + j] = share_p(j), n = P * N values
  * (fp32 handles: widened to double).  ACS_EINVAL on any handle not made by acs_create_csr_split. */
 int acs_get_split_shares(struct acs_sim* sim, double* out, uint64_t n);
+
+/* DESIGN.md §9 ("Push-sum with messages in transit"): rule PUSHSUM under bounded delays.  A message
+ * sent in round r on slot e arrives in round r + delta, delta = draw(DELAY, b, r, e) mod
+ * (transit_max + 1) with b the global instance id; until then its mass is in transit on the link, so
+ * node mass plus transit mass is conserved and the run converges to the mean.  (acs_config.delay_max
+ * is another model, a stale read of values, and stays refused for PUSHSUM.)  A message that is
+ * dropped, or down under the schedule, in the round it is sent never enters transit: its mass is
+ * lost, as under OMIT.  The EPS test looks at x alone: a run may stop with mass in transit.
+ * period, avail: a link schedule as for acs_create_csr_scheduled, or 0, NULL for none.
+ * transit_max = 0 computes what acs_create_csr_weighted / _scheduled computes, bit for bit.
+ * Checked on the host before any device call: a rule other than PUSHSUM, missing_policy = HOLD,
+ * delay_max > 0 (ACS_EUNSUPPORTED); transit_max > 64, ACS_F32 with max_rounds above
+ * floor(2^26 / (16 + transit_max)) (ACS_EINVAL); and every check of acs_create_csr_weighted /
+ * acs_create_csr_scheduled.  The ring of pending pairs takes B * (transit_max + 1) * nnz pairs of
+ * device memory (ACS_ENOMEM when that fails). */
+int acs_create_csr_transit(const acs_config* cfg, const uint64_t* rowptr, const uint32_t* colidx,
+                           const double* w_self, const double* w_edge,
+                           uint32_t period, const uint32_t* avail,   /* 0, NULL: no schedule */
+                           uint32_t transit_max, int device, struct acs_sim** out);
+/* The mass in transit, ACS_EINVAL on any handle not made by acs_create_csr_transit (and on a
+ * transit_max = 0 handle with n != 0).  Planes are relative to the instance's own executed rounds R:
+ * acs_get_pushsum_transit: out[d * nnz + e], d = 0 .. transit_max - 1, is what round R + d will
+ * deliver on slot e from messages already sent; n >= transit_max * nnz values of the config dtype
+ * into each of h_out and k_out.
+ * acs_set_pushsum_transit: n = B * transit_max * nnz values in each array, instance-major, each
+ * instance plane-major as above.  |h| <= 1e290 (ACS_F32: 1e26), k finite, >= 0 and within the same
+ * cap; -0.0 is stored as +0.0.  acs_set_state and acs_set_pushsum_state empty the planes, so a resume
+ * with mass in flight calls acs_set_pushsum_transit after them. */
+int acs_get_pushsum_transit(struct acs_sim* sim, uint64_t instance, void* h_out, void* k_out, uint64_t n);
+int acs_set_pushsum_transit(struct acs_sim* sim, const void* h, const void* k, uint64_t n);
 
 /* §8(e) node partitioning of ONE RANDOM_REGULAR instance over n_ranks GPUs (cfg5), one process
  * (or thread) per GPU.  Rank r owns the 64-aligned row block [r*R, (r+1)*R) ∩ [0, N),
