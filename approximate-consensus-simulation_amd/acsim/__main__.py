@@ -21,6 +21,9 @@
   python -m acsim run --graph scheduled.npz --set rule=pushsum --split
       (push-sum with per-round splitting on the file's schedule, DESIGN.md §9: no weights, no held
       state, and the mean is kept; reported on stderr)
+  python -m acsim run --graph g.npz --set rule=weighted --quant 8 --quant-mode compensated --quant-dither
+      (rule weighted with quantized messages, DESIGN.md §9: every node transmits its state on the grid
+      of step 2**-8; reported on stderr)
 """
 from __future__ import annotations
 
@@ -65,7 +68,7 @@ def _grid(specs):
     return grid
 
 
-def validate(cfg: Config, csr=None, weights=None, schedule=None, split=False, transit=None) -> int:
+def validate(cfg: Config, csr=None, weights=None, schedule=None, split=False, transit=None, quant=None) -> int:
     """Host-side §A.8 validation through the library (no GPU needed: acs_create validates first)."""
     lib = _abi.load_library()
     c = cfg.to_c()
@@ -78,6 +81,17 @@ def validate(cfg: Config, csr=None, weights=None, schedule=None, split=False, tr
         rc = lib.acs_create_csr_split(C.byref(c), rp.ctypes.data_as(C.POINTER(C.c_uint64)),
                                       ci.ctypes.data_as(C.POINTER(C.c_uint32)), int(period),
                                       av.ctypes.data_as(C.POINTER(C.c_uint32)), 0, C.byref(h))
+    elif csr is not None and weights is not None and quant is not None:
+        from .graphs import quant_args
+        rp, ci = np.ascontiguousarray(csr[0], dtype=np.uint64), np.ascontiguousarray(csr[1], dtype=np.uint32)
+        ws, we = (np.ascontiguousarray(w, dtype=np.float64) for w in weights)
+        av = None if schedule is None else np.ascontiguousarray(schedule[1], dtype=np.uint32)
+        dp = C.POINTER(C.c_double)
+        rc = lib.acs_create_csr_quantized(C.byref(c), rp.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                          ci.ctypes.data_as(C.POINTER(C.c_uint32)), ws.ctypes.data_as(dp),
+                                          we.ctypes.data_as(dp), 0 if schedule is None else int(schedule[0]),
+                                          None if av is None else av.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                          *quant_args(quant, cfg.dtype), 0, C.byref(h))
     elif csr is not None and weights is not None and transit is not None:
         rp, ci = np.ascontiguousarray(csr[0], dtype=np.uint64), np.ascontiguousarray(csr[1], dtype=np.uint32)
         ws, we = (np.ascontiguousarray(w, dtype=np.float64) for w in weights)
@@ -135,6 +149,13 @@ def main(argv=None) -> int:
         p.add_argument("--transit", type=int, metavar="D",
                        help="rule pushsum with messages in transit for up to D rounds (0 .. 64), on the graph file's "
                             "weights and link schedule")
+        p.add_argument("--quant", type=int, metavar="K",
+                       help="rule weighted with quantized messages: every node transmits its state on the grid of "
+                            "step 2**-K (0 .. 52, dtype f32: 0 .. 23)")
+        p.add_argument("--quant-mode", choices=sorted(_abi.QUANT_MODES), default=None,
+                       help="with --quant: what a node averages its neighbours' quantized states with (default partial)")
+        p.add_argument("--quant-dither", action="store_true",
+                       help="with --quant: round up with probability equal to the fractional part, not to nearest")
         if name in ("run", "sweep"):
             p.add_argument("--out")
         if name == "sweep":
@@ -155,6 +176,25 @@ def main(argv=None) -> int:
             ap.error("--transit is not served with --split")
         if not 0 <= a.transit <= _abi.TRANSIT_MAX:
             ap.error(f"--transit must be in 0 .. {_abi.TRANSIT_MAX}")
+    quant = None
+    if a.quant is None and (a.quant_mode is not None or a.quant_dither):
+        ap.error("--quant-mode and --quant-dither need --quant")
+    if a.quant is not None:
+        from .config import _enum
+        from .graphs import quant_args
+        if not a.graph:
+            ap.error("--quant needs --graph")
+        if a.split or a.transit is not None:
+            ap.error("--quant is not served with --split or --transit")
+        if _enum("rule", cfg.rule) != _abi.RULE_WEIGHTED:
+            ap.error("--quant needs --set rule=weighted")
+        quant = (a.quant, a.quant_mode or "partial", bool(a.quant_dither))
+        try:
+            quant_args(quant, cfg.dtype)
+        except ValueError as e:
+            ap.error(str(e))
+        print(f"weighted: quantized messages, step 2**-{quant[0]}, mode {quant[1]}, "
+              f"{'dithered' if quant[2] else 'rounded to nearest'}", file=sys.stderr)
     if a.graph:
         from .config import _enum
         from .graphs import load_csr
@@ -205,7 +245,7 @@ def main(argv=None) -> int:
                   "in transit until then", file=sys.stderr)
         cfg = cfg.replace(topology="csr", n_nodes=int(csr[0].size - 1))
     if a.cmd == "validate":
-        rc = validate(cfg, csr, weights, schedule, split=a.split, transit=a.transit)
+        rc = validate(cfg, csr, weights, schedule, split=a.split, transit=a.transit, quant=quant)
         if rc == 0:
             print("ok")
         return rc
@@ -213,7 +253,7 @@ def main(argv=None) -> int:
         from .io import save_result
         from .sim import simulate
         res = simulate(cfg, device=a.device, return_values=bool(a.out), csr=csr, weights=weights, schedule=schedule,
-                       split=a.split, transit=a.transit)
+                       split=a.split, transit=a.transit, quant=quant)
         from .sweep import summarize
         print(json.dumps(summarize(cfg, res)))
         if a.out:
@@ -221,7 +261,7 @@ def main(argv=None) -> int:
         return 0
     from .sweep import sweep
     rows = sweep(cfg, _grid(a.grid), out_dir=a.out, device=a.device, csr=csr, weights=weights, schedule=schedule,
-                 split=a.split, transit=a.transit)
+                 split=a.split, transit=a.transit, quant=quant)
     for r in rows:
         print(json.dumps(r))
     return 0

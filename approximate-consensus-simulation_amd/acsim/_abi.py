@@ -30,9 +30,14 @@ MISSING_SELF, MISSING_OMIT = 0, 1
 MISSING_HOLD = 2   # rule PUSHSUM only: a dropped message's mass waits on the link
 SCHEDULE_MAX_PERIOD = 32   # link schedules: one uint32 mask per CSR slot
 TRANSIT_MAX = 64           # push-sum with messages in transit: the largest transit bound
+# quantized messages: what entry 0 of a row is, and whether the error is added back
+QUANT_PARTIAL, QUANT_TOTAL, QUANT_COMPENSATED = 0, 1, 2
+QUANT_MODES = {"partial": QUANT_PARTIAL, "total": QUANT_TOTAL, "compensated": QUANT_COMPENSATED}
+QUANT_MAX_LOG2 = {"f64": 52, "f32": 23}   # the step is 2^-k with 0 <= k <= this
 
 STREAM_INIT, STREAM_DROP, STREAM_FAULTSET, STREAM_CRASH_ROUND = 0, 1, 2, 3
 STREAM_CRASH_PARTIAL, STREAM_BYZ, STREAM_GRAPH = 4, 5, 6
+STREAM_DELAY, STREAM_QUANT = 7, 8
 
 STATUS_HONEST = 0xFFFFFFFF
 STATUS_BYZANTINE = 0xFFFFFFFE
@@ -126,6 +131,9 @@ def _declare(lib: C.CDLL) -> None:
                                          u32, i32, P(vp)]),
         "acs_get_pushsum_transit": (i32, [vp, u64, vp, vp, u64]),
         "acs_set_pushsum_transit": (i32, [vp, vp, vp, u64]),
+        "acs_create_csr_quantized": (i32, [P(AcsConfig), P(u64), P(u32), P(C.c_double), P(C.c_double), u32, P(u32),
+                                           u32, u32, u32, i32, P(vp)]),
+        "acs_get_quantized": (i32, [vp, u64, vp, u64]),
         "acs_comm_id_size": (i32, []),
         "acs_get_comm_id": (i32, [vp, u64]),
         "acs_create_partitioned": (i32, [P(AcsConfig), i32, i32, i32, vp, u64, P(vp)]),

@@ -250,6 +250,71 @@ def split_shares(rowptr, colidx, period, avail, dtype="f64"):
     return _floor_recip(c, dtype)
 
 
+def quant_args(quant, dtype="f64"):
+    """(k, mode, dither) of Simulator(..., quant=...) as the three integers acs_create_csr_quantized
+    takes: the step is 2**-k, mode is "partial", "total" or "compensated", dither a bool."""
+    from . import _abi
+    try:
+        k, mode, dither = quant
+    except (TypeError, ValueError):
+        raise ValueError("quant must be (k, mode, dither)") from None
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
+        raise ValueError("quant: k must be an integer")
+    kmax = _abi.QUANT_MAX_LOG2["f32" if str(dtype) in ("f32", "float32") else "f64"]
+    if not 0 <= int(k) <= kmax:
+        raise ValueError(f"quant: k must be in [0, {kmax}] (dtype {dtype}): the step is 2**-k")
+    if not isinstance(mode, str) or mode not in _abi.QUANT_MODES:
+        raise ValueError(f"quant: mode must be one of {sorted(_abi.QUANT_MODES)}")
+    if not isinstance(dither, (bool, np.bool_)):
+        raise ValueError("quant: dither must be a bool")
+    return int(k), _abi.QUANT_MODES[mode], int(bool(dither))
+
+
+def quantize(x, k, dither=False, seed=0, instance=0, round=0, dtype=None):
+    """What the nodes transmit under Simulator(..., quant=(k, mode, dither)): Q(x) on
+    the grid of step 2**-k.  x[N] holds node i's state at index i; seed is the config's, instance the
+    global instance id (instance_offset + local index) and round the round in which the values are
+    sent.  dither False: rint(x * 2**k) * 2**-k, half to even.  dither True: floor(x * 2**k) plus one
+    where draw(QUANT, instance, round, i) < uint32(frac * 2**32).  Every step is exact in x's dtype
+    (float32 stays float32, everything else is float64, unless dtype says otherwise); -0.0 never
+    comes out."""
+    from . import _abi
+    x = np.asarray(x)
+    ft = np.float32 if (str(dtype) in ("f32", "float32") if dtype is not None else x.dtype == np.float32) else np.float64
+    if isinstance(k, (bool, np.bool_)) or int(k) != k or not 0 <= int(k) <= _abi.QUANT_MAX_LOG2["f32" if ft is np.float32 else "f64"]:
+        raise ValueError("quantize: k must be an integer in [0, 52] (float32: [0, 23])")
+    x = x.astype(ft)
+    if x.ndim != 1:
+        raise ValueError("quantize: x must be one instance's values, x[N]")
+    u = np.ldexp(x, int(k)).astype(ft)
+    if dither:
+        f = np.floor(u)
+        thr = np.ldexp(u - f, 32).astype(np.uint64)
+        w = _draw(int(seed), _abi.STREAM_QUANT, int(instance), int(round), np.arange(x.size, dtype=np.uint64))
+        n = f + (w.astype(np.uint64) < thr).astype(ft)
+    else:
+        n = np.rint(u)
+    return (np.ldexp(n, -int(k)).astype(ft) + ft(0)).astype(ft)
+
+
+def _draw(seed, stream, b, r, s):
+    """draw(stream, b, r, s) = philox4x32-10((s >> 2, r, b, stream), key(seed))[s & 3]
+    for a uint64 array s; uint32 values."""
+    m32 = np.uint64(0xFFFFFFFF)
+    s = np.asarray(s, dtype=np.uint64)
+    c = [s >> np.uint64(2), np.full(s.shape, r & 0xFFFFFFFF, np.uint64), np.full(s.shape, b & 0xFFFFFFFF, np.uint64),
+         np.full(s.shape, stream, np.uint64)]
+    k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64((seed >> 32) & 0xFFFFFFFF)
+    for rnd in range(10):
+        if rnd:
+            k0 = (k0 + np.uint64(0x9E3779B9)) & m32
+            k1 = (k1 + np.uint64(0xBB67AE85)) & m32
+        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k0, p1 & m32, (p0 >> np.uint64(32)) ^ c[3] ^ k1, p0 & m32]
+    sel = (s & np.uint64(3)).astype(np.intp)
+    return np.choose(sel, c).astype(np.uint32)
+
+
 def column_sums(rowptr, colidx, w_self, w_edge):
     """Column sums of the weight matrix: w_self[j] plus every w_edge[slot] with colidx[slot] == j,
     each as a correctly rounded sum (math.fsum).  Rule "pushsum" needs every one <= 1 + 2^-30."""

@@ -45,7 +45,7 @@ class Simulator:
 
     def __init__(self, cfg: Config | str, device: int = 0, backend: str = "hip",
                  partitions: int = 1, rank: int = 0, comm_id: Optional[bytes] = None,
-                 csr=None, weights=None, schedule=None, split=False, transit=None):
+                 csr=None, weights=None, schedule=None, split=False, transit=None, quant=None):
         """partitions > 1 node-partitions one RANDOM_REGULAR instance: with
         comm_id (RCCL unique id from acsim.distributed) this handle is `rank`'s partition on
         `device`; without it all partitions are simulated on `device` with private x copies
@@ -69,7 +69,14 @@ class Simulator:
         messages in transit"): a message sent in round r arrives in round r + delta, delta drawn per slot and
         round from 0 .. D, and until then its mass is in transit on the link, so the run still finds the
         mean.  A schedule may be given too.  transit=None (the default) is the handle without delays;
-        transit=0 computes the same values through the transit kernels."""
+        transit=0 computes the same values through the transit kernels.
+
+        quant=(k, mode, dither) with csr, weights and rule="weighted" ("Quantized messages"):
+        every node transmits its state on the grid of step 2**-k (0 <= k <= 52, dtype="f32": 23), rounded
+        to nearest (dither false) or up with probability equal to the fractional part (dither true).
+        mode "partial": a node averages its own exact state with its neighbours' quantized ones;
+        "total": its own quantized state too; "compensated": as "total", then adds its own quantization
+        error back, which keeps the mean.  A schedule may be given too; faults and delays are refused."""
         if isinstance(cfg, str):
             cfg = preset(cfg)
         if backend != "hip":
@@ -99,6 +106,14 @@ class Simulator:
             if not 0 <= int(transit) <= _abi.TRANSIT_MAX:
                 raise ValueError(f"transit must be in [0, {_abi.TRANSIT_MAX}]")
             self._transit = int(transit)
+        self._quant = None
+        if quant is not None:
+            from .graphs import quant_args
+            if csr is None or weights is None:
+                raise ValueError("quant needs a csr graph with weights (rule 'weighted')")
+            if split or transit is not None:
+                raise ValueError("quant is not served with split=True or transit")
+            self._quant = quant_args(quant, cfg.dtype)
         if split:   # rule="pushsum" with per-round splitting (acs_create_csr_split)
             from .graphs import check_schedule, full_schedule
             rp = np.ascontiguousarray(csr[0], dtype=np.uint64)
@@ -123,7 +138,17 @@ class Simulator:
                 raise ValueError("weights must be (w_self[n_nodes], w_edge[len(colidx)])")
             self._nnz = int(ci.size)
             dp = C.POINTER(C.c_double)
-            if self._transit is not None:   # push-sum with messages in transit (acs_create_csr_transit)
+            if self._quant is not None:   # rule "weighted" with quantized messages (acs_create_csr_quantized)
+                period, av = 0, None
+                if schedule is not None:
+                    from .graphs import check_schedule
+                    period, av = check_schedule(rp, schedule[0], schedule[1], values=False)
+                rc = self._lib.acs_create_csr_quantized(
+                    C.byref(self._c), rp.ctypes.data_as(C.POINTER(C.c_uint64)), ci.ctypes.data_as(C.POINTER(C.c_uint32)),
+                    ws.ctypes.data_as(dp), we.ctypes.data_as(dp), period,
+                    None if av is None else av.ctypes.data_as(C.POINTER(C.c_uint32)), *self._quant, int(device),
+                    C.byref(h))
+            elif self._transit is not None:   # push-sum with messages in transit (acs_create_csr_transit)
                 period, av = 0, None
                 if schedule is not None:
                     from .graphs import check_schedule
@@ -393,6 +418,15 @@ class Simulator:
         self._chk(self._lib.acs_get_split_shares(self._h, out.ctypes.data_as(C.POINTER(C.c_double)), out.size))
         return out
 
+    def quantized(self, instance: int = 0) -> np.ndarray:
+        """[N] what the nodes of one instance of a handle made with quant=... transmit in its next round
+        R (its executed rounds): Q(x^R), in the config dtype."""
+        if self._quant is None:
+            raise ValueError("quantized needs a handle made with quant=(k, mode, dither)")
+        out = np.empty(self.N, dtype=self.value_dtype)
+        self._chk(self._lib.acs_get_quantized(self._h, int(instance), out.ctypes.data, out.size))
+        return out
+
     def neighbors(self) -> np.ndarray:
         d = int(self.cfg.degree)
         out = np.empty(self.N * d, dtype=np.uint32)
@@ -423,7 +457,7 @@ class Simulator:
 
 def simulate(cfg: Config | str, backend: str = "hip", device: int = 0,
              devices: Optional[Sequence[int]] = None, return_values: bool = True,
-             csr=None, weights=None, schedule=None, split=False, transit=None) -> Result:
+             csr=None, weights=None, schedule=None, split=False, transit=None, quant=None) -> Result:
     """Run one configuration to termination and return its results."""
     if devices is not None:
         devices = list(devices)
@@ -432,7 +466,7 @@ def simulate(cfg: Config | str, backend: str = "hip", device: int = 0,
                              "processes with acsim.distributed (one rank per GPU)")
         device = devices[0]
     with Simulator(cfg, device=device, backend=backend, csr=csr, weights=weights, schedule=schedule,
-                   split=split, transit=transit) as sim:
+                   split=split, transit=transit, quant=quant) as sim:
         res = sim.run()
         x = None
         if return_values:

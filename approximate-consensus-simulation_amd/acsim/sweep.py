@@ -39,16 +39,17 @@ def summarize(cfg: Config, res) -> Dict:
 
 def sweep(base: Config, grid: Dict[str, Iterable], out_dir: Optional[str] = None, device: int = 0,
           run: Optional[Callable] = None, keep_values: bool = False, csr=None, weights=None,
-          schedule=None, split: bool = False, transit: Optional[int] = None) -> List[Dict]:
+          schedule=None, split: bool = False, transit: Optional[int] = None, quant=None) -> List[Dict]:
     """run(cfg) -> Result (default: acsim.simulate on `device`; csr: a user graph for
     topology="csr" configs, shared by every point; weights: its (w_self, w_edge) for rule="weighted"; schedule: its link
     schedule (period, avail), passed on with the weights; split: rule="pushsum" with per-round splitting on
-    that schedule, no weights; transit: rule="pushsum" with messages in transit for up to that many rounds)."""
+    that schedule, no weights; transit: rule="pushsum" with messages in transit for up to that many rounds;
+    quant: rule="weighted" with quantized messages, (k, mode, dither))."""
     if run is None:
         from .sim import simulate
         run = lambda c: simulate(c, device=device, return_values=keep_values or out_dir is not None,  # noqa: E731
                                  csr=csr, weights=weights, schedule=schedule, split=split,
-                                 transit=transit)
+                                 transit=transit, quant=quant)
     rows = []
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)

@@ -5,6 +5,7 @@
 #include <chrono>
 
 #include "handle.hpp"
+#include "quantize.hpp"
 
 using namespace acs;
 
@@ -142,6 +143,52 @@ int acs_create_csr_transit(const acs_config* cfg, const uint64_t* rowptr, const 
     const LinkSchedule sched{period, avail};   // (checked with the arrays: sched_check.hpp)
     return create_impl(cfg, device, 1, 0, nullptr, 0, out, rowptr, colidx, w_self, w_edge, period ? &sched : nullptr,
                        (int)transit_max);
+}
+
+int acs_create_csr_quantized(const acs_config* cfg, const uint64_t* rowptr, const uint32_t* colidx, const double* w_self,
+                             const double* w_edge, uint32_t period, const uint32_t* avail, uint32_t step_log2, uint32_t mode,
+                             uint32_t dither, int device, acs_sim** out) {
+    if (out) *out = nullptr;
+    if (!cfg || cfg->topology != ACS_TOPO_CSR) return fail(ACS_EINVAL, "config topology must be ACS_TOPO_CSR");
+    if (cfg->rule != ACS_RULE_WEIGHTED)
+        return fail(ACS_EUNSUPPORTED, "quantized messages are served for rule WEIGHTED (got rule %u): quantizing "
+                                      "push-sum's pairs loses mass", cfg->rule);
+    if (!rowptr || !colidx) return fail(ACS_EINVAL, "null CSR arrays");
+    if (!w_self || !w_edge) return fail(ACS_EINVAL, "null weight arrays");
+    if (!out) return fail(ACS_EINVAL, "null out");
+    if (period == 0 && avail) return fail(ACS_EINVAL, "a link schedule needs period >= 1 (no schedule: 0, NULL)");
+    if (int rc = validate(cfg)) return rc;   // (before the refusals: an invalid config is ACS_EINVAL first)
+    const uint32_t kmax = cfg->dtype == ACS_F32 ? kQuantMaxLog2F32 : kQuantMaxLog2F64;
+    if (step_log2 > kmax)
+        return fail(ACS_EINVAL, "quantized messages: step_log2 must be <= %u%s (got %u): the step 2^-step_log2 keeps "
+                                "every operation exact", kmax, cfg->dtype == ACS_F32 ? " in fp32" : "", step_log2);
+    if (mode > ACS_QUANT_COMPENSATED)
+        return fail(ACS_EINVAL, "quantized messages: mode must be ACS_QUANT_PARTIAL, _TOTAL or _COMPENSATED (got %u)", mode);
+    if (dither > 1) return fail(ACS_EINVAL, "quantized messages: dither must be 0 or 1 (got %u)", dither);
+    if (cfg->fault_model != ACS_FAULT_NONE)
+        return fail(ACS_EUNSUPPORTED, "quantized messages are not served with a fault model (fault_model = %u)",
+                    cfg->fault_model);
+    if (cfg->delay_max > 0)
+        return fail(ACS_EUNSUPPORTED, "quantized messages are not served with delay_max > 0 (got %u): a delayed read "
+                                      "would need every past round's quantized values", cfg->delay_max);
+    const LinkSchedule sched{period, avail};   // (checked with the arrays: sched_check.hpp)
+    const QuantSpec quant{step_log2, mode, dither};
+    return create_impl(cfg, device, 1, 0, nullptr, 0, out, rowptr, colidx, w_self, w_edge, period ? &sched : nullptr, -1,
+                       &quant);
+}
+
+int acs_get_quantized(acs_sim* s, uint64_t b, void* out, uint64_t n) {
+    if (!s || !out) return fail(ACS_EINVAL, "null argument");
+    if (!s->quant) return fail(ACS_EINVAL, "acs_get_quantized: not a handle of acs_create_csr_quantized");
+    if (b >= s->B || n < s->N) return fail(ACS_EINVAL, "bad get_quantized arguments (instance < B, n >= N)");
+    HIP_TRY(hipSetDevice(s->device));
+    InstState e;
+    HIP_TRY(hipMemcpyAsync(&e, s->st + b, sizeof e, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpyAsync(out, static_cast<char*>(quant_at(s, e.rounds)) + b * s->N * s->es, s->N * s->es,
+                           hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return ACS_OK;
 }
 
 // The instance's relative plane d = 0 .. tmax - 1 (what round R + d delivers, R its executed rounds)
@@ -503,6 +550,8 @@ int acs_set_state(acs_sim* s, uint32_t round, const void* x, uint64_t n) {
             if (!(fabsf(xf[k]) <= 1e30f)) return fail(ACS_EINVAL, "set_state: value %llu is not finite or |x| > 1e30", (unsigned long long)k);
             if (s->pushsum && !(fabsf(xf[k]) <= kPushsumMaxAbs32))
                 return fail(ACS_EINVAL, "set_state: value %llu has |x| > 1e26 (PUSHSUM, fp32)", (unsigned long long)k);
+            if (s->quant && !(fabsf(xf[k]) <= kPushsumMaxAbs32))   // (|x| * 2^k stays finite)
+                return fail(ACS_EINVAL, "set_state: value %llu has |x| > 1e26 (quantized messages, fp32)", (unsigned long long)k);
             cf[k] = xf[k] + 0.0f;
         }
     } else {
@@ -512,6 +561,8 @@ int acs_set_state(acs_sim* s, uint32_t round, const void* x, uint64_t n) {
             if (!(fabs(xd[k]) <= 1e300)) return fail(ACS_EINVAL, "set_state: value %llu is not finite or |x| > 1e300", (unsigned long long)k);
             if (s->pushsum && !(fabs(xd[k]) <= kPushsumMaxAbs64))
                 return fail(ACS_EINVAL, "set_state: value %llu has |x| > 1e290 (PUSHSUM)", (unsigned long long)k);
+            if (s->quant && !(fabs(xd[k]) <= kPushsumMaxAbs64))   // (|x| * 2^k stays finite)
+                return fail(ACS_EINVAL, "set_state: value %llu has |x| > 1e290 (quantized messages)", (unsigned long long)k);
             cd[k] = xd[k] + 0.0;
         }
     }
@@ -532,6 +583,9 @@ int acs_set_state(acs_sim* s, uint32_t round, const void* x, uint64_t n) {
     if (s->split)     // the offers of round `round`: its phase's shares of the new pairs
         HIP_TRY(launch_pushsum_offer(pairs_at(s, round), share_at(s, round), offers_at(s, round), s->B, s->N, s->f32,
                                      s->stream));
+    if (s->quant)     // what the nodes transmit in round `round`: a pure function of (x, b, round, i)
+        HIP_TRY(launch_quantize(xb(s, round), quant_at(s, round), s->B, s->N, round, s->mp, s->qk, s->qdither, s->f32,
+                                s->stream));
     if (s->hold)      // and every link empty (a resume with held mass calls acs_set_pushsum_links next)
         HIP_TRY(hipMemsetAsync(s->links, 0, links_bytes(s), s->stream));
     if (s->transit)   // and nothing in transit (a resume with mass in flight calls acs_set_pushsum_transit next)

@@ -225,6 +225,7 @@ void release(acs_sim* s) {
     (void)hipFree(s->avell);
     (void)hipFree(s->share);
     (void)hipFree(s->offers);
+    (void)hipFree(s->qbuf);
     (void)hipFree(s->gen_ids);
     (void)hipFree(s->crank);
     (void)hipFree(s->clist);
@@ -361,9 +362,9 @@ static uint64_t decide_binned(acs_sim* s, const CreateOptions& o) {
     // CSR rows padded to a degree with a weighted phase B and no fault schedule (loss is served: phase
     // B draws its own drop mask); every other weighted handle, and every PUSHSUM handle (16-byte
     // pairs), keeps its per-lane kernel; so does every handle with a link schedule (phase B has no
-    // availability test).
+    // availability test) and every handle with quantized messages (phase A stages x, not what the nodes transmit).
     const bool rule_binned = s->weighted ? o.bin.weighted && c.rule == ACS_RULE_WEIGHTED && !s->f32 && s->csr_var && !s->sched &&
-                                               c.fault_model == ACS_FAULT_NONE && binned_weighted_supported(s->d)
+                                               !s->quant && c.fault_model == ACS_FAULT_NONE && binned_weighted_supported(s->d)
                                          : binned_supported(s->d, c.trim, c.rule);
     s->binned = o.bin.enabled && f32_tags_ok && s->path == PATH_REGULAR && c.delay_max == 0 &&
                 !(s->csr_var && s->f32) &&
@@ -683,7 +684,8 @@ static std::string kernel_name_of(const acs_sim* s) {
         if (faults) nm += regular_plan && s->bin.fix ? "+k_bin_fixup" : "+k_bin_tag";
         if (s->bin_sb != kBinSB) nm += " sb" + std::to_string(s->bin_sb);
     } else if (s->csr_var) {
-        const std::string w = "<" + std::to_string(s->d) + (s->sched ? ",csr,sched>" : ",csr>");   // (SCHED instantiations)
+        // (SCHED instantiations; k_round_weighted's QUANT ones)
+        const std::string w = "<" + std::to_string(s->d) + (s->sched ? ",csr,sched" : ",csr") + (s->quant ? ",quant>" : ">");
         // (k_round_pushsum_hold, k_round_pushsum_transit: the reported names of k_round_pushsum's kLinkHold and
         // kLinkTransit instantiations)
         nm = s->split    ? "k_round_pushsum_split<" + std::to_string(s->d) + ",csr>"
@@ -718,6 +720,10 @@ static int finish_handle(acs_sim* s, const CreateOptions& o, const void* comm_id
     if (s->split) {   // round 0's offers: phase 0's shares of (x^0, 1)
         STAGE_TRY(hipMalloc(&s->offers, 2 * s->B * s->N * 2 * s->es));
         STAGE_TRY(launch_pushsum_offer(pairs_at(s, 0), share_at(s, 0), offers_at(s, 0), s->B, s->N, s->f32, s->stream));
+    }
+    if (s->quant) {   // what the nodes transmit in round 0: Q(x^0; b, 0, i)
+        STAGE_TRY(hipMalloc(&s->qbuf, 2 * s->B * s->N * s->es));
+        STAGE_TRY(launch_quantize(s->x[0], quant_at(s, 0), s->B, s->N, 0, s->mp, s->qk, s->qdither, s->f32, s->stream));
     }
     if (s->hold) {   // every link starts empty: (+0.0, +0.0)
         STAGE_TRY(hipMalloc(&s->links, links_bytes(s)));
@@ -805,7 +811,8 @@ static int check_arguments(const acs_config* cfg, int device, int nranks, int ra
 
 // The handle's fields that follow from the config, the partition arguments and the path alone.
 static acs_sim* new_handle(const acs_config& c, int device, int nranks, int rank, bool partitioned, bool virt,
-                           const PathChoice& pc, const CsrCheck& chk, const LinkSchedule* h_sched, int transit_max) {
+                           const PathChoice& pc, const CsrCheck& chk, const LinkSchedule* h_sched, int transit_max,
+                           const QuantSpec* h_quant) {
     acs_sim* s = new acs_sim();
     s->c = c;
     s->device = device;
@@ -829,6 +836,8 @@ static acs_sim* new_handle(const acs_config& c, int device, int nranks, int rank
     s->sched = h_sched != nullptr;
     s->period = h_sched ? h_sched->period : 0;
     s->split = h_sched && h_sched->split;
+    s->quant = h_quant != nullptr;   // (acs_create_csr_quantized: rule WEIGHTED, no faults, no delays)
+    if (h_quant) s->qk = h_quant->k, s->qmode = h_quant->mode, s->qdither = h_quant->dither;
     // "clean": no slot-dependent decision at all (no faults, no loss, no delays, no link schedule)
     s->clean = c.fault_model == ACS_FAULT_NONE && drop_threshold(c.loss_p) == 0 && c.delay_max == 0 && !s->sched;
     s->mp.key = key_of(c.seed);
@@ -855,7 +864,7 @@ static acs_sim* new_handle(const acs_config& c, int device, int nranks, int rank
 
 int create_impl(const acs_config* cfg, int device, int nranks, int rank, const void* comm_id, uint64_t id_len,
                 acs_sim** out, const uint64_t* h_rowptr, const uint32_t* h_colidx, const double* h_wself,
-                const double* h_wedge, const LinkSchedule* h_sched, int transit_max) {
+                const double* h_wedge, const LinkSchedule* h_sched, int transit_max, const QuantSpec* h_quant) {
     *out = nullptr;
     // 1. host checks and 2. path choice, before any handle exists
     CsrCheck chk;
@@ -867,7 +876,8 @@ int create_impl(const acs_config* cfg, int device, int nranks, int rank, const v
     if (int rc = choose_path(*cfg, opt, partitioned, chk.mmax, h_rowptr, pc)) return rc;
 
     RoctxRange range("acs: create (graph, plan, fault schedule, x0)");
-    acs_sim* s = new_handle(*cfg, device, nranks, rank, partitioned, partitioned && !comm_id, pc, chk, h_sched, transit_max);
+    acs_sim* s = new_handle(*cfg, device, nranks, rank, partitioned, partitioned && !comm_id, pc, chk, h_sched, transit_max,
+                            h_quant);
     // 3. - 7.: the order matters in three places.  eacc (alloc_state) exists before any
     // binned_build, whose bin_desc reads it; the fault status is built before the plans, whose fix-up
     // list reads it; and `binned` is decided (decide_binned) before the fp32 crash-rank table.

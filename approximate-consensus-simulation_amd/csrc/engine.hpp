@@ -19,6 +19,8 @@
 //   share, offers : rule PUSHSUM with per-round splitting only: the share table
 //               [period][N] of the config dtype, and two buffers [B][N] of offers (share * pair) by
 //               round parity, beside pairs; such a handle has no wself / wedge / well and no links
+//   quant     : rule WEIGHTED with quantized messages only: two buffers [B][N] of the
+//               config dtype by round parity, beside x: what every node transmits in that round
 //   status    : u32 [B][N] fault status (§A.4), absent when there are no faults
 //   st        : InstState [B] — honest lo/hi/spread of the current round, rounds, done flags
 //   partial   : double2 [B][nblk] per-block honest (min, max) partials of x^{r+1} (§A.8)
@@ -132,6 +134,13 @@ struct RoundArgs {
     // slot's receiver.  nullptr for every other handle.
     void* trn;
     uint32_t trn_cur, trn_np;
+    // rule WEIGHTED with quantized messages (handles of acs_create_csr_quantized): what
+    // every node transmits in round r (qin) and in round r + 1 (qout, which the round writes beside
+    // xout), instance-major [B][N] of the config dtype; step 2^-qk, qmode = ACS_QUANT_*, qdither 0 / 1.
+    // nullptr for every other handle.
+    const void* qin;
+    void* qout;
+    uint32_t qk, qmode, qdither;
 };
 constexpr uint32_t kEaccSlots = 32, kEaccStride = 16;       // eacc pairs, u64 words between pairs
 constexpr uint32_t kEaccWords = kEaccSlots * kEaccStride;   // eacc words of one round parity
@@ -237,6 +246,11 @@ hipError_t launch_weights_to_ell(const uint64_t* rowptr, const void* wedge, cons
 // (setup.hip) a link schedule's masks, slot order -> the same order (0 in absent columns and hub rows)
 hipError_t launch_avail_to_ell(const uint64_t* rowptr, const uint32_t* avail, const uint8_t* deg, uint64_t N,
                                uint32_t d, uint32_t* avell, hipStream_t s);
+
+// (round_weighted.hip) q[b][i] = Q(x[b][i]; inst_offset + b, r, i) for B instances of N nodes (create,
+// acs_set_state): what a quantized handle's nodes transmit in round r (quantize.hpp)
+hipError_t launch_quantize(const void* x, void* q, uint64_t B, uint64_t N, uint32_t r, const MsgParams& mp, uint32_t k,
+                           uint32_t dither, bool f32, hipStream_t s);
 
 // Rule PUSHSUM on a CSR graph (round_pushsum.hip): one lane per receiver over the same padded ELL
 // and weight array, a pair gather per sender; hub rows are skipped (k_round_generic's rule-6 branch).

@@ -182,7 +182,12 @@ struct acs_sim {
     bool split = false;
     void* share = nullptr;
     void* offers = nullptr;
-    double* dsorted = nullptr;     // dense path: sorted base multiset [N]
+    // rule WEIGHTED with quantized messages (handles of acs_create_csr_quantized): what
+    // every node transmits, two buffers [B][N] of the config dtype by round parity, beside x
+    bool quant = false;
+    uint32_t qk = 0, qmode = 0, qdither = 0;   // step 2^-qk, ACS_QUANT_*, 0 / 1
+    void* qbuf = nullptr;
+    double* dsorted = nullptr;    // dense path: sorted base multiset [N]
     uint32_t* dcounts = nullptr;   // dense path: |B|, #Byzantine, #crash-silent
     std::vector<Part> parts;       // virtual partitions 1..P-1 (partition 0 uses x / ell)
     // kernel timing (bench)
@@ -242,6 +247,10 @@ static inline void* offers_at(const acs_sim* s, uint32_t q) {
 static inline void* share_at(const acs_sim* s, uint32_t q) {
     return static_cast<char*>(s->share) + (uint64_t)(q % s->period) * s->N * s->es;
 }
+// quantized messages: the buffer of what the nodes transmit in round q
+static inline void* quant_at(const acs_sim* s, uint32_t q) {
+    return static_cast<char*>(s->qbuf) + (uint64_t)(q & 1u) * s->B * s->N * s->es;
+}
 // rule PUSHSUM under HOLD: bytes of the link buffer (at least one pair, so the pointer is never null)
 static inline uint64_t links_bytes(const acs_sim* s) { return (s->B * s->nnz ? s->B * s->nnz : 1) * 2 * s->es; }
 // ... with messages in transit: bytes of one plane of one instance, and of the whole ring (at least
@@ -264,12 +273,16 @@ struct LinkSchedule {   // acs_create_csr_scheduled's arguments as given (sched_
     const uint32_t* avail;
     bool split = false;   // acs_create_csr_split: no weights, shares from the schedule (split_shares.hpp)
 };
+struct QuantSpec {      // acs_create_csr_quantized's arguments (api.hip checks them)
+    uint32_t k, mode, dither;
+};
 int validate(const acs_config* c);   // §A.8 constraints
 // A handle for a validated config (the callers in api.hip validate); *out is null on any failure.
 int create_impl(const acs_config* cfg, int device, int nranks, int rank, const void* comm_id, uint64_t id_len,
                 acs_sim** out, const uint64_t* h_rowptr = nullptr, const uint32_t* h_colidx = nullptr,
                 const double* h_wself = nullptr, const double* h_wedge = nullptr,
-                const LinkSchedule* h_sched = nullptr, int transit_max = -1);   // >= 0: acs_create_csr_transit
+                const LinkSchedule* h_sched = nullptr, int transit_max = -1,   // >= 0: acs_create_csr_transit
+                const QuantSpec* h_quant = nullptr);                           // acs_create_csr_quantized
 void release(acs_sim* s);
 
 // ---- rounds.hip

@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <mutex>
 
+#include "quantize.hpp"
 #include "resolve.hpp"
 #include "sortnet.hpp"
 
@@ -183,11 +184,27 @@ __global__ __launch_bounds__(BLK) void k_round_generic(const RoundArgs a, uint32
         // past m) adds +0.0 to both.  A zero weight sum (OMIT only) keeps x_i.
         const VT* __restrict__ ws = reinterpret_cast<const VT*>(a.wself);
         const VT* __restrict__ we = reinterpret_cast<const VT*>(a.wedge);
+        // quantized messages (a.qin; k_round_weighted's QUANT instantiations; no faults, no delays): a
+        // sender's entry is what it transmits, qin[j]; entry 0, which a missing entry takes under SELF,
+        // is x_i in mode PARTIAL and qin[i] otherwise; COMPENSATED adds x_i - qin[i] to the quotient, and
+        // what the row transmits next is stored with x_i'.
+        const VT* __restrict__ qin = a.qin ? reinterpret_cast<const VT*>(a.qin) + lb * N : nullptr;
+        const VT qi = qin ? qin[i] : xi;
+        const VT e0 = qin && a.qmode != kQuantPartial ? qi : xi;
         for (uint32_t e = threadIdx.x; e < P; e += BLK) {
             VT pe = VT(0), wt = VT(0);
             if (e < m) {
-                bool out;
-                const VT v = generic_entry<VT>(a, lb, b, bG, i, rp, e, x, stv, xi, lo, hi, out);
+                bool out = false;
+                VT v = e0;
+                if (!qin) {
+                    v = generic_entry<VT>(a, lb, b, bG, i, rp, e, x, stv, xi, lo, hi, out);
+                } else if (e != 0) {
+                    const uint64_t slot = rp + e - 1;
+                    if (slot_missing(a, mp, bG, a.r, slot))
+                        out = mp.omit != 0;
+                    else
+                        v = qin[a.colidx[slot]];
+                }
                 if (!out) {
                     wt = e == 0 ? ws[i] : we[rp + e - 1];
                     pe = wt * v + VT(0);
@@ -200,7 +217,11 @@ __global__ __launch_bounds__(BLK) void k_round_generic(const RoundArgs a, uint32
         const VT num = block_tree_sum<BLK>(sh, P);
         const VT den = block_tree_sum<BLK>(sh + P, P);
         if (threadIdx.x == 0) {
-            const VT res = den > VT(0) ? num / den : xi;
+            VT res = den > VT(0) ? num / den : xi;
+            if (qin) {
+                if (den > VT(0) && a.qmode == kQuantCompensated) res = res + (xi - qi);
+                (reinterpret_cast<VT*>(a.qout) + lb * N)[i] = quantize<VT>(res, a.qk, a.qdither, mp.key, b, a.r + 1, i);
+            }
             xo[i] = res;
             *part = honest ? make_double2((double)res, (double)res) : make_double2(kInf, -kInf);
         }

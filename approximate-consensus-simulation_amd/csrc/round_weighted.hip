@@ -15,6 +15,7 @@
 //   - honest (min, max) of x^{r+1} reduced per block -> one partial (§A.8 epilogue).
 // Hub rows (deg[i] = kDegHub) are left to k_round_generic's rule-5 branch.
 #include "csr_lane.hpp"
+#include "quantize.hpp"
 #include "resolve.hpp"
 #include "rules.hpp"
 
@@ -25,7 +26,13 @@ namespace acs {
 // Once all groups are issued the masks are reduced to one bit per column, set when the slot is down
 // in this round (so they are dead before the gathers); a down slot's message is missing exactly as
 // a dropped one.
-template <int D, typename VT, bool SCHED>
+//
+// QUANT ("Quantized messages"; no faults, no delays): the gathers read what the senders
+// transmit (a.qin) and never x; entry 0, which a missing entry also takes under SELF, is x_i in mode
+// PARTIAL and q_i = qin[i] otherwise; COMPENSATED adds the node's own quantization error x_i - q_i
+// to the quotient.  The lane then stores what node i transmits in the next round beside
+// x_i' (a.qout): one more load and store per lane, and one Philox call under dither.
+template <int D, typename VT, bool SCHED, bool QUANT>
 __global__ __launch_bounds__(kRegularBlock) void k_round_weighted(const RoundArgs a) {
     static_assert(D % 4 == 0, "compiled widths are multiples of 4");
     constexpr int M = D + 1;
@@ -44,6 +51,13 @@ __global__ __launch_bounds__(kRegularBlock) void k_round_weighted(const RoundArg
     if (i < N && a.deg[i] != kDegHub) {
         const VT xi = x[i];
         VT res = xi;
+        const VT* __restrict__ qin = nullptr;
+        VT qi = xi, e0 = xi;   // e0: entry 0
+        if constexpr (QUANT) {
+            qin = reinterpret_cast<const VT*>(a.qin) + lb * N;
+            qi = qin[i];
+            e0 = a.qmode == kQuantPartial ? xi : qi;
+        }
         bool honest = true, active = true;
         const uint32_t* stv = nullptr;   // null: no fault schedule
         if (a.status) {
@@ -102,23 +116,28 @@ __global__ __launch_bounds__(kRegularBlock) void k_round_weighted(const RoundArg
             for (int t = 0; t < D; ++t) {
                 const bool ok = (uint32_t)t < dg;
                 const uint32_t j = ok ? col[t] : i;
+                if constexpr (QUANT) {
+                    xj[t] = ok ? qin[j] : e0;
+                    sj[t] = kHonest;
+                    continue;
+                }
                 if (a.delay)
                     xj[t] = ok ? delayed_x<VT>(a, lb, r, draw(mp.key, kStreamDelay, b, r, rp + t), j) : xi;
                 else
                     xj[t] = ok ? x[j] : xi;
                 sj[t] = (ok && stv) ? stv[j] : kHonest;
             }
-            p[0] = w[0] * xi + VT(0);
+            p[0] = w[0] * e0 + VT(0);
 #pragma unroll
             for (int t = 0; t < D; ++t) {
                 bool gone = (uint32_t)t >= dg;   // absent column: +0.0 in both sums (w is +0.0 already)
-                VT u = xi;
+                VT u = e0;
                 if (!gone) {
                     const uint64_t s = rp + t;
                     bool dropped = mp.thr && draw(mp.key, kStreamDrop, bG, r, s) < mp.thr;
                     if (SCHED) dropped = dropped || ((down >> t) & 1u);
                     bool miss;
-                    u = resolve_entry_m(mp, sj[t], xj[t], xi, dropped, b, r, i, s, lo, hi, miss);
+                    u = resolve_entry_m(mp, sj[t], xj[t], e0, dropped, b, r, i, s, lo, hi, miss);
                     gone = mp.omit && miss;   // SELF: the entry takes x_i and keeps its weight
                 }
                 const VT wt = gone ? VT(0) : w[1 + t];
@@ -127,8 +146,14 @@ __global__ __launch_bounds__(kRegularBlock) void k_round_weighted(const RoundArg
             }
             const VT num = tree_sum_const<M>(p), den = tree_sum_const<M>(w);
             if (den > VT(0)) res = num / den;   // den = 0: every present weight is 0 (OMIT) -> keep x_i
+            if constexpr (QUANT) {
+                if (den > VT(0) && a.qmode == kQuantCompensated) res = res + (xi - qi);
+            }
         }
         xo[i] = res;
+        if constexpr (QUANT)
+            (reinterpret_cast<VT*>(a.qout) + lb * N)[i] =
+                quantize<VT>(res, a.qk, a.qdither, a.mp.key, (uint32_t)(a.mp.inst_offset + lb), a.r + 1, i);
         if (honest) {
             mn = res;
             mx = res;
@@ -140,12 +165,40 @@ __global__ __launch_bounds__(kRegularBlock) void k_round_weighted(const RoundArg
 // ---------------------------------------------------------------------------- dispatch
 hipError_t launch_round_weighted(const RoundArgs& a, uint64_t B, uint32_t nblk_fast, hipStream_t s) {
     if (!a.deg || !a.sw || !a.ell || !a.well || !a.wself || !a.rowptr) return hipErrorInvalidValue;
+    if ((a.qin != nullptr) != (a.qout != nullptr) || (a.qin && (a.status || a.delay))) return hipErrorInvalidValue;
     const dim3 grid((unsigned)nblk_fast, (unsigned)B);
     const dim3 block(kRegularBlock);
     const bool hit = csr_lane_select(a, [&](auto d, auto vt, auto sched) {
-        hipLaunchKernelGGL((k_round_weighted<decltype(d)::value, decltype(vt), decltype(sched)::value>), grid, block, 0, s, a);
+        constexpr int DD = decltype(d)::value;
+        constexpr bool SC = decltype(sched)::value;
+        if (a.qin)
+            hipLaunchKernelGGL((k_round_weighted<DD, decltype(vt), SC, true>), grid, block, 0, s, a);
+        else
+            hipLaunchKernelGGL((k_round_weighted<DD, decltype(vt), SC, false>), grid, block, 0, s, a);
     });
     return hit ? hipGetLastError() : hipErrorNotSupported;
+}
+
+// q[b][i] = Q(x[b][i]; inst_offset + b, r, i)
+template <typename VT>
+__global__ __launch_bounds__(256) void k_quantize(const VT* __restrict__ x, VT* __restrict__ q, uint64_t N, uint32_t r,
+                                                  Key key, uint64_t inst_offset, uint32_t k, uint32_t dither) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const uint64_t at = (uint64_t)blockIdx.y * N + i;
+    q[at] = quantize<VT>(x[at], k, dither, key, (uint32_t)(inst_offset + blockIdx.y), r, (uint32_t)i);
+}
+
+hipError_t launch_quantize(const void* x, void* q, uint64_t B, uint64_t N, uint32_t r, const MsgParams& mp, uint32_t k,
+                           uint32_t dither, bool f32, hipStream_t s) {
+    const dim3 grid((unsigned)((N + 255) / 256), (unsigned)B);
+    if (f32)
+        hipLaunchKernelGGL(k_quantize<float>, grid, dim3(256), 0, s, static_cast<const float*>(x), static_cast<float*>(q), N,
+                           r, mp.key, mp.inst_offset, k, dither);
+    else
+        hipLaunchKernelGGL(k_quantize<double>, grid, dim3(256), 0, s, static_cast<const double*>(x), static_cast<double*>(q),
+                           N, r, mp.key, mp.inst_offset, k, dither);
+    return hipGetLastError();
 }
 
 }  // namespace acs

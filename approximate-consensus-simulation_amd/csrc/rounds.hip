@@ -174,6 +174,13 @@ static RoundArgs round_args(acs_sim* s, uint32_t r) {
         a.oout = offers_at(s, r + 1);
         a.share_next = share_at(s, r + 1);
     }
+    if (s->quant) {   // (what the nodes transmit in this round was stored with x^r)
+        a.qin = quant_at(s, r);
+        a.qout = quant_at(s, r + 1);
+        a.qk = s->qk;
+        a.qmode = s->qmode;
+        a.qdither = s->qdither;
+    }
     return a;
 }
 

@@ -34,7 +34,8 @@ extern "C" {
                                   likewise ACS_SCHEDULE_MAX_PERIOD, acs_create_csr_scheduled and
                                   acs_get_link_schedule; likewise acs_create_csr_split and
                                   acs_get_split_shares; likewise acs_create_csr_transit and
-                                  acs_get / acs_set_pushsum_transit) */
+                                  acs_get / acs_set_pushsum_transit; likewise ACS_STREAM_QUANT,
+                                  ACS_QUANT_*, acs_create_csr_quantized and acs_get_quantized) */
 
 /* status codes */
 #define ACS_OK            0
@@ -124,6 +125,13 @@ extern "C" {
 #define ACS_STREAM_BYZ           5u
 #define ACS_STREAM_GRAPH         6u
 #define ACS_STREAM_DELAY         7u   /* bounded-delay rounds */
+#define ACS_STREAM_QUANT         8u   /* dither of quantized messages */
+
+/* quantized messages ("Quantized messages"; acs_create_csr_quantized): what entry 0
+ * of a receiver's row is, and whether the quantization error is added back */
+#define ACS_QUANT_PARTIAL     0   /* entry 0 is x_i; x_i' = y */
+#define ACS_QUANT_TOTAL       1   /* entry 0 is q_i; x_i' = y */
+#define ACS_QUANT_COMPENSATED 2   /* entry 0 is q_i; x_i' = y + (x_i - q_i): the mean is kept */
 
 /* Opaque simulation handle. */
 typedef struct acs_sim acs_sim;
@@ -281,6 +289,28 @@ int acs_create_csr_transit(const acs_config* cfg, const uint64_t* rowptr, const 
  * with mass in flight calls acs_set_pushsum_transit after them. */
 int acs_get_pushsum_transit(struct acs_sim* sim, uint64_t instance, void* h_out, void* k_out, uint64_t n);
 int acs_set_pushsum_transit(struct acs_sim* sim, const void* h, const void* k, uint64_t n);
+
+/* DESIGN.md §9 ("Quantized messages"): rule WEIGHTED on links that carry a finite number of bits.
+ * Every node transmits q = Q(x), its state on the grid of step 2^-step_log2, and the rule's arithmetic
+ * runs on those values unchanged.  Q(x; b, r, i) for node i of global instance b in round r:
+ * u = x * 2^k; dither = 0: n = rint(u) (half to even); dither = 1: f = floor(u), g = u - f,
+ * n = f + (draw(QUANT, b, r, i) < (uint32)(g * 2^32)); q = n * 2^-k + 0.0.  Every step is exact in the
+ * config dtype.  Sender entries are q_j; entry 0, which a missing entry also takes under SELF, is x_i
+ * (ACS_QUANT_PARTIAL) or q_i (ACS_QUANT_TOTAL, ACS_QUANT_COMPENSATED); y = num / den; x_i' = y, or
+ * y + (x_i - q_i) under ACS_QUANT_COMPENSATED; a zero weight sum keeps x_i.
+ * period, avail: a link schedule as for acs_create_csr_scheduled, or 0, NULL for none.
+ * Checked on the host before any device call: a rule other than WEIGHTED, a fault model, delay_max > 0
+ * (ACS_EUNSUPPORTED); step_log2 > 52 (ACS_F32: 23), mode > 2, dither > 1 (ACS_EINVAL); and every check
+ * of acs_create_csr_weighted / acs_create_csr_scheduled.  acs_set_state on such a handle admits
+ * |x| <= 1e290 (ACS_F32: 1e26) and recomputes q. */
+int acs_create_csr_quantized(const acs_config* cfg, const uint64_t* rowptr, const uint32_t* colidx,
+                             const double* w_self, const double* w_edge,
+                             uint32_t period, const uint32_t* avail,   /* 0, NULL: no schedule */
+                             uint32_t step_log2, uint32_t mode, uint32_t dither, int device,
+                             struct acs_sim** out);
+/* What the instance's nodes transmit in its next round R (its executed rounds): q^R = Q(x^R; b, R, .),
+ * n >= N values of the config dtype.  ACS_EINVAL on any handle not made by acs_create_csr_quantized. */
+int acs_get_quantized(struct acs_sim* sim, uint64_t instance, void* out, uint64_t n);
 
 /* §8(e) node partitioning of ONE RANDOM_REGULAR instance over n_ranks GPUs (cfg5), one process
  * (or thread) per GPU.  Rank r owns the 64-aligned row block [r*R, (r+1)*R) ∩ [0, N),
